@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py — decode-step throughput of the MI355X paged-attention hot path.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A PLAIN run does what the headline figure needs and nothing else: set up, W warm-up steps, ONE timed region of exactly K steps,
+the outputs of the last step to DIR if --dump-outputs is given, the result line.  Everything else described below — the kernel
+event pass and the roofline, the CPU baseline, every sub-record, the repeated timed regions, for N > 1 the exchange's own pass and
+the legacy-method figure — runs with --full only (`--full --headline-only`: the headline, its kernel pass and its roofline).
 
 N = 1 runs in this process.  N > 1 with no WORLD_SIZE in the environment LAUNCHES ITSELF: this process starts N
 ranks of this same file (one per GPU, RANK/LOCAL_RANK/WORLD_SIZE/MASTER_ADDR=127.0.0.1 set), waits for them and
@@ -43,8 +48,15 @@ Beside `value` (never as it), each a sub-record of the same line:
                 trace of ragged requests, batched admission, refills, preemption by swap — generated tokens/s, per-token latency,
                 occupancy, host us per step beside the GPU wait, swap traffic (`--serve` alone runs the 2048-request trace)
 
-The headline's timed region holds EXACTLY K steps; a region shorter than --min-timed-ms (50) is repeated and the line reports the
-MEDIAN region with every region listed (`ms_per_step_regions`).  The e2e records report the median of three regions.
+The headline's timed region holds EXACTLY K steps.  With --full a region shorter than --min-timed-ms (50) is repeated and the line
+reports the MEDIAN region with every region listed (`ms_per_step_regions`); a plain run times one region, so --steps is the number
+of timed steps.  The e2e records report the median of three regions.
+
+--dump-outputs DIR writes what the LAST timed step left for its caller, as float32 .npy files: `out` (the attention output,
+[batch, heads, head_size]), `key_cache_rows` / `value_cache_rows` (the cache rows at that step's slot_mapping, [batch, kv_heads,
+head_size]) and `key_cache_blocks` / `value_cache_blocks` (up to 64 of the blocks that step wrote into, whole, a seeded choice).  fp8
+caches are written as their byte codes.  The workload is seeded, so two runs with the same arguments hold the same inputs and two
+builds can be compared file by file.  Rank r > 0 of an N > 1 run writes `<name>_rank<r>.npy`.
 
 Multi-GPU: sequences are sharded over ranks as independent KV pools, no collective on the data
 path.  --scaling weak (default): 256 sequences per GPU, pool of 65536 blocks (BASELINE configs[4]); --scaling strong:
@@ -84,6 +96,12 @@ def build_parser():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline too: kernel event pass + roofline, CPU baseline, the sub-records, "
+                         "repeated timed regions (a plain run times ONE region of --steps steps and prints the headline alone)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last one left for its caller (out, the cache rows and blocks it "
+                         "wrote) as float32 DIR/<name>.npy")
     ap.add_argument("--config", default="cfg3", choices=sorted(CONFIGS))
     ap.add_argument("--batch", type=int, default=0, help="override the config's batch (diagnostic sweeps)")
     ap.add_argument("--pv-mfma", action="store_true",
@@ -132,7 +150,8 @@ def build_parser():
     ap.add_argument("--serve-eager", action="store_true", help="plain launches instead of hipGraph replay")
     ap.add_argument("--no-serve", action="store_true", help="skip the extra serving-loop measurement")
     ap.add_argument("--min-timed-ms", type=float, default=50.0,
-                    help="repeat the K-step timed region until the regions hold this many ms in all; the line reports the MEDIAN region")
+                    help="--full: repeat the K-step timed region until the regions hold this many ms in all; the line reports the "
+                         "MEDIAN region")
     ap.add_argument("--headline-only", action="store_true",
                     help="only the headline call pair: no sub-records, no CPU baseline (what the rocprofv3 passes run)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -175,6 +194,8 @@ def build_parser():
 
 def parse_args(argv=None):
     args = build_parser().parse_args(argv)
+    if not args.full:      # a plain run: the headline alone, one timed region of exactly --steps steps
+        args.headline_only, args.min_timed_ms = True, 0.0
     if args.headline_only:
         args.no_cpu_baseline = args.no_fused = args.no_fp8 = args.no_ragged = args.no_graph = True
         args.no_cfg4 = args.no_e2e = args.no_cfg2 = args.no_strong = args.no_long = args.no_deferred = args.no_serve = True
@@ -1158,6 +1179,70 @@ def random_fp8_codes(shape, dev, gen):
             | (torch.randint(0, 2, shape, dtype=torch.uint8, device=dev, generator=gen) << 7))
 
 
+DUMP_BLOCKS = 64       # whole cache blocks per --dump-outputs file (cfg3: 3 MB each as float32)
+
+
+def dump_outputs(directory, wl, out, steps, rank=0):
+    """--dump-outputs: what the last of `steps` timed steps left for its caller — `out`, and of the two caches, which it
+    updates in place and which are far larger than a dump may be, the rows at that step's slot_mapping and DUMP_BLOCKS whole
+    blocks among those it wrote into (a seeded choice) — as float32 <name>.npy under `directory`."""
+    import numpy as np
+
+    c = wl.cfg
+    t = (steps - 1) % len(wl.tables)
+    slots = wl.slots[(t + 1) % len(wl.tables) if RESHAPE_OTHER else t]
+    blk, off = slots // c.block_size, slots % c.block_size
+    pick = torch.from_numpy(np.sort(np.random.default_rng(0).permutation(c.batch)[:DUMP_BLOCKS])).to(blk.device)
+    arrays = {"out": out,
+              "key_cache_rows": wl.key_cache[blk, :, :, off, :].reshape(c.batch, c.kv_heads, c.head_size),
+              "value_cache_rows": wl.value_cache[blk, :, :, off],
+              "key_cache_blocks": wl.key_cache[blk[pick]],
+              "value_cache_blocks": wl.value_cache[blk[pick]]}
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + (f"_rank{rank}" if rank else "") + ".npy"), a.float().cpu().numpy())
+
+
+def kernel_fields(args, cfg, ks, line_bytes, vname):
+    """--full: what the kernel event pass (`ks`, kernel_stats) and the profiler passes committed under profiles/ add to the
+    headline's line — the attention kernel's duration, the roofline from it, the committed traffic and kernel figures."""
+    achieved = line_bytes / (ks["median"] * 1e-6) / 1e9
+    traffic, traffic_src = (pmc_traffic(cfg.name + {"auto": "", "fp8": "_fp8", "fp8_e5m2": "_fp8_e5m2"}[args.kv], vname) if args.op == "v1" else
+                            pmc_traffic(cfg.name + "_" + args.op, vname) if args.op in ("fused", "newest") else (None, None))
+    fields = {
+        "paged_attention_v1_us_per_step": ks["median"],
+        "paged_attention_v1_us_median": ks["median"],
+        "paged_attention_v1_us_mean": ks["mean"],
+        "paged_attention_v1_us_min": ks["min"],
+        "paged_attention_v1_us_median_per_rank": ks["median_per_rank"],
+        "kernel_event_samples": args.kernel_samples,
+        "committed_profile_kernel_us": rocprof_kernel_us(cfg.name if cfg.name != "cfg5" else "cfg3", vname)[0] if args.op == "v1" and args.kv == "auto" and not args.ragged else None,
+        "kernel_event_pass": "separate from the timed region: one HIP event pair around every attention launch of "
+                             f"{args.kernel_samples} call pairs; roofline.achieved uses the median",
+        "roofline": {
+            "bound": "hbm",
+            "achieved": achieved,
+            "peak": HBM_PEAK_GBPS,
+            "unit": "GB/s",
+            "frac": achieved / HBM_PEAK_GBPS,
+            "traffic": traffic,
+            "traffic_source": traffic_src,
+            "kernel": "pa_q_kernel" if vname.startswith(("q_d", "bf16_q_d", "fp8_q_d")) else "pa_v1_kernel",
+            "algorithmic_bytes_per_launch": line_bytes,
+            **({"mfma": "q.K^T of the K pass", "mfma_note": "fp8 pages: the decoded K tile is the B operand of v_mfma_f32_16x16x32_f16, q "
+                "the A operand with 16 equal rows — 1 of 16 result rows is useful work, the matrix pipe is otherwise idle; "
+                "p.V stays on the VALU (profiles/r03b_k_pass_on_mfma.md)"} if vname.endswith("m") and "_q_d" in vname else
+               {"mfma": 0, "mfma_note": "multi-head decode is M = 1 per KV head: both contractions are GEMVs, the kernel "
+                                        "issues no MFMA (SQ_INSTS_MFMA = 0, profiles/pmc_cfg3_latest.json)"}),
+        },
+    }
+    if fields["committed_profile_kernel_us"]:
+        # what the HIP event pair around a launch reads above the kernel's own duration in the committed rocprofv3 pass of this
+        # binary (dispatch-to-dispatch spacing, event records): the instrumentation share of roofline.achieved's denominator
+        fields["event_minus_rocprof_us"] = ks["median"] - fields["committed_profile_kernel_us"]
+    return fields
+
+
 def main(argv=None):
     global KV_DTYPE, SKIP_RESHAPE, RESHAPE_OTHER, NOOP_RESHAPE
     argv = list(sys.argv[1:] if argv is None else argv)
@@ -1254,20 +1339,19 @@ def main(argv=None):
     elapsed = statistics.median(regions)
     tokens = cfg.batch * world * args.steps          # one new token per sequence per step
     ms_per_step = elapsed / args.steps * 1e3
-    # ---- the attention kernel's duration: its own pass ------------------------------------------------------------------
-    ks = kernel_stats(kernel_pass(wl, out, args.kernel_samples, args.variant, dev, op=args.op), dist, dev)
+    if args.dump_outputs:      # the last timed step's results, before any other pass writes `out` and the caches again
+        dump_outputs(args.dump_outputs, wl, out, args.steps, rank)
+    # ---- the attention kernel's duration: its own pass (--full) ----------------------------------------------------------
+    ks = kernel_stats(kernel_pass(wl, out, args.kernel_samples, args.variant, dev, op=args.op), dist, dev) if args.full else None
     line_bytes = alg_bytes(cfg)
     if args.ragged or args.ragged_sorted:      # the bytes that exist in THIS batch (lengths differ), not the config's
         tok = int(wl.seq_lens.sum().item())
         line_bytes = 2 * tok * cfg.kv_heads * cfg.head_size * (1 if args.kv.startswith("fp8") else 2) + \
             2 * cfg.batch * cfg.num_heads * cfg.head_size * 2 + \
             int(((wl.seq_lens + cfg.block_size - 1) // cfg.block_size).sum().item()) * 4 + cfg.batch * 4
-    achieved = line_bytes / (ks["median"] * 1e-6) / 1e9
     # the variant the library actually launched (it knows the launch's kv_scale, the pick queries do not)
     vid = args.variant or (ops.last_variant() if args.op in ("v1", "fused", "newest") else 0)
     vname = ops.variant_names()[vid - 1] if vid else f"paged_attention_v2 variant {args.variant or 'auto'}"
-    traffic, traffic_src = (pmc_traffic(cfg.name + {"auto": "", "fp8": "_fp8", "fp8_e5m2": "_fp8_e5m2"}[args.kv], vname) if args.op == "v1" else
-                            pmc_traffic(cfg.name + "_" + args.op, vname) if args.op in ("fused", "newest") else (None, None))
     line = {
         "metric": "decode_tokens_per_sec_paged_attention_v1_per_layer",
         "value": tokens / elapsed,
@@ -1302,55 +1386,31 @@ def main(argv=None):
             "launch": "self-launched ranks" if os.environ.get("VMI_BENCH_SELF_LAUNCHED") == "1" else
                       ("external launcher" if dist is not None else "single process"),
         },
-        "paged_attention_v1_us_per_step": ks["median"],
-        "paged_attention_v1_us_median": ks["median"],
-        "paged_attention_v1_us_mean": ks["mean"],
-        "paged_attention_v1_us_min": ks["min"],
-        "paged_attention_v1_us_median_per_rank": ks["median_per_rank"],
-        "kernel_event_samples": args.kernel_samples,
+        "full": args.full,
         "library_sha16": library_sha16(),
-        "committed_profile_kernel_us": rocprof_kernel_us(cfg.name if cfg.name != "cfg5" else "cfg3", vname)[0] if args.op == "v1" and args.kv == "auto" and not args.ragged else None,
         "method_version": 3,
         "method": "v3 (round 3 on): event-free timed region; " + shard.TIMING_BRACKET + "; for N > 1 the token all_gather runs "
                   f"once per token (every {EXCHANGE_EVERY}th layer step), asynchronously on the process group's stream.  v2 (rounds "
                   "1-2): a blocking all_gather on EVERY step, clock stopped behind the closing barrier — for N > 1 the line carries "
                   "that figure too (`legacy_method_step`), so round-over-round comparisons need not mix method and kernel changes",
         "timing_bracket": shard.TIMING_BRACKET,
-        "kernel_event_pass": "separate from the timed region: one HIP event pair around every attention launch of "
-                             f"{args.kernel_samples} call pairs; roofline.achieved uses the median",
-        "roofline": {
-            "bound": "hbm",
-            "achieved": achieved,
-            "peak": HBM_PEAK_GBPS,
-            "unit": "GB/s",
-            "frac": achieved / HBM_PEAK_GBPS,
-            "traffic": traffic,
-            "traffic_source": traffic_src,
-            "kernel": "pa_q_kernel" if vname.startswith(("q_d", "bf16_q_d", "fp8_q_d")) else "pa_v1_kernel",
-            "algorithmic_bytes_per_launch": line_bytes,
-            **({"mfma": "q.K^T of the K pass", "mfma_note": "fp8 pages: the decoded K tile is the B operand of v_mfma_f32_16x16x32_f16, q "
-                "the A operand with 16 equal rows — 1 of 16 result rows is useful work, the matrix pipe is otherwise idle; "
-                "p.V stays on the VALU (profiles/r03b_k_pass_on_mfma.md)"} if vname.endswith("m") and "_q_d" in vname else
-               {"mfma": 0, "mfma_note": "multi-head decode is M = 1 per KV head: both contractions are GEMVs, the kernel "
-                                        "issues no MFMA (SQ_INSTS_MFMA = 0, profiles/pmc_cfg3_latest.json)"}),
-        },
+        "roofline": None,          # (--full: the kernel event pass's figures, kernel_fields)
     }
-    if line.get("committed_profile_kernel_us"):
-        # what the HIP event pair around a launch reads above the kernel's own duration in the committed rocprofv3 pass of this
-        # binary (dispatch-to-dispatch spacing, event records): the instrumentation share of roofline.achieved's denominator
-        line["event_minus_rocprof_us"] = ks["median"] - line["committed_profile_kernel_us"]
+    if args.full:
+        line.update(kernel_fields(args, cfg, ks, line_bytes, vname))
     if dist is not None:
-        line["token_exchange_us"] = shard.max_over_ranks(exchange_pass(args.kernel_samples, dist, dev), dist, dev)
         line["token_exchange"] = (f"all_gather of {cfg.batch} int64 ids per rank ({cfg.batch * world * 8} B in all), backend nccl "
                                   f"(RCCL); inside the timed region once per token = on every {EXCHANGE_EVERY}th layer step "
                                   f"(steps 0, {EXCHANGE_EVERY}, ...), issued ASYNCHRONOUSLY on the process group's stream — a rank "
                                   "samples its own sequences' ids, the next token's layers do not wait for the gathered vector — "
-                                  "and waited for one token later and before the closing synchronise; token_exchange_us = median "
-                                  f"of {args.kernel_samples} BLOCKING exchanges alone, by HIP events")
+                                  "and waited for one token later and before the closing synchronise; token_exchange_us (--full) = "
+                                  f"median of {args.kernel_samples} BLOCKING exchanges alone, by HIP events")
         line["token_exchange_every_steps"] = EXCHANGE_EVERY
         line["rccl_ranks"] = dist.get_world_size()          # ranks in the process group (backend "nccl" = RCCL on ROCm)
         line["process_group_backend"] = dist.get_backend()
         line["rank_placement"] = shard.gather_objects(_PLACEMENT, dist)     # per rank: device uuid / PCI id, NUMA node, bound cores
+    if dist is not None and args.full:
+        line["token_exchange_us"] = shard.max_over_ranks(exchange_pass(args.kernel_samples, dist, dev), dist, dev)
         # the SAME K steps the way rounds 1-2 measured them: blocking exchange on every step, clock behind the barrier
         l_elapsed = shard.max_over_ranks(time_steps(wl, out, args.steps, args.warmup, args.variant, dist, dev, op=args.op, legacy=True),
                                          dist, dev)

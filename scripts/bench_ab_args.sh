@@ -8,7 +8,7 @@ for ARGS in "$@"; do
   for i in 1 2 3; do
     for v in old new; do
       cp /tmp/$v.so vllmini_amd/_C/libvmi_paged_attention.so
-      python bench.py --steps 200 --warmup 30 --headline-only --kernel-samples 120 $ARGS 2>/dev/null | python -c "
+      python bench.py --full --steps 200 --warmup 30 --headline-only --kernel-samples 120 $ARGS 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('$v', '[$ARGS]', d['config']['kernel_variant'], 'step_us %.1f' % (d['ms_per_step']*1e3), 'kernel_us median %.1f min %.1f' % (d['paged_attention_v1_us_median'], d['paged_attention_v1_us_min']))"

@@ -3,12 +3,12 @@
 # the serving record at full trace length.  Usage: scripts/evidence_round.sh <tag>
 T=${1:-r06z}
 O=gpurun_out
-python bench.py > $O/${T}_bench_cfg3.json 2> $O/${T}_bench_cfg3.err
+python bench.py --full > $O/${T}_bench_cfg3.json 2> $O/${T}_bench_cfg3.err
 LIGHT="--no-e2e --no-serve --no-deferred --no-long --no-strong --no-cfg4 --no-cfg2 --no-cpu-baseline"
-VMI_FORCE_DIST=1 python bench.py --gpus 1 $LIGHT > $O/${T}_bench_forced_dist_n1.json 2> $O/${T}_bench_forced_dist_n1.err
-VMI_FORCE_DIST=1 python bench.py --gpus 1 --scaling strong $LIGHT > $O/${T}_bench_forced_dist_n1_strong.json 2> $O/${T}_bench_forced_dist_n1_strong.err
-python bench.py --headline-only > $O/${T}_bench_headline_only.json 2> /dev/null
-python bench.py --scaling strong --config cfg5_strong --headline-only > $O/${T}_bench_strong_plain_n1.json 2> /dev/null
+VMI_FORCE_DIST=1 python bench.py --full --gpus 1 $LIGHT > $O/${T}_bench_forced_dist_n1.json 2> $O/${T}_bench_forced_dist_n1.err
+VMI_FORCE_DIST=1 python bench.py --full --gpus 1 --scaling strong $LIGHT > $O/${T}_bench_forced_dist_n1_strong.json 2> $O/${T}_bench_forced_dist_n1_strong.err
+python bench.py --full --headline-only > $O/${T}_bench_headline_only.json 2> /dev/null
+python bench.py --full --scaling strong --config cfg5_strong --headline-only > $O/${T}_bench_strong_plain_n1.json 2> /dev/null
 python bench.py --serve 2> $O/${T}_serve.err; cp $O/serve.json $O/${T}_serve.json
 python bench.py --serve --serve-preempt drop 2> /dev/null; cp $O/serve.json $O/${T}_serve_drop.json
 python bench.py --serve --serve-no-deferred-scatter 2> /dev/null; cp $O/serve.json $O/${T}_serve_call_pair.json

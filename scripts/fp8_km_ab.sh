@@ -9,7 +9,7 @@ elif [ "$CFG" = cfg4 ]; then VARS="fp8_q_d128_s1q2 fp8_q_d128_s1q2m"; else VARS=
 for r in 1 2 3; do
   for v in $VARS; do
     for rag in "" "--ragged"; do
-      python bench.py --config $CFG --kv $KV --variant-name $v --headline-only --steps 200 --warmup 20 --kernel-samples 100 $rag 2>/dev/null | python -c "
+      python bench.py --full --config $CFG --kv $KV --variant-name $v --headline-only --steps 200 --warmup 20 --kernel-samples 100 $rag 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('%-18s %-9s step_us %7.1f  kernel_us median %7.1f mean %7.1f min %7.1f' % ('$v', '$rag' or 'equal', d['ms_per_step']*1e3, d['paged_attention_v1_us_median'], d['paged_attention_v1_us_mean'], d['paged_attention_v1_us_min']))"

@@ -460,7 +460,7 @@ def test_driver_entry_points_compile_and_parse_arguments():
         py_compile.compile(os.path.join(REPO, f), doraise=True)
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--help"], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-2000:]
-    for flag in ("--gpus", "--steps", "--warmup"):
+    for flag in ("--gpus", "--steps", "--warmup", "--full", "--dump-outputs"):
         assert flag in r.stdout
 
 

@@ -144,6 +144,53 @@ def test_launch_decision_and_cpu_thread_candidates():
     h = bench.parse_args(["--headline-only"])
     assert h.no_cpu_baseline and h.no_fused and h.no_fp8 and h.no_ragged and h.no_graph and h.no_cfg4 and h.no_e2e
     assert h.no_cfg2 and h.no_strong
+    # a plain run is the headline alone, ONE timed region of --steps steps; --full is the whole line
+    p = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert not p.full and p.headline_only and p.min_timed_ms == 0 and not p.dump_outputs
+    assert p.no_cpu_baseline and p.no_fused and p.no_fp8 and p.no_ragged and p.no_graph and p.no_cfg4 and p.no_e2e
+    assert p.no_cfg2 and p.no_strong and p.no_long and p.no_deferred and p.no_serve
+    f = bench.parse_args(["--full"])
+    assert f.full and not f.headline_only and f.min_timed_ms == 50
+    assert not (f.no_cpu_baseline or f.no_fused or f.no_fp8 or f.no_ragged or f.no_graph or f.no_cfg4 or f.no_e2e
+                or f.no_cfg2 or f.no_strong or f.no_long or f.no_deferred or f.no_serve)
+    fh = bench.parse_args(["--full", "--headline-only"])
+    assert fh.full and fh.no_e2e and fh.no_cpu_baseline and fh.min_timed_ms == 50
     assert bench.cpu_thread_candidates(256, 128) == [8, 16, 32, 64, 128, 256]
     assert bench.cpu_thread_candidates(8, 4) == [1, 2, 4, 8]
     assert bench.cpu_thread_candidates(2, 1) == [1, 2]
+
+
+def test_dump_outputs_writes_the_last_steps_rows_and_blocks(tmp_path):
+    """bench.dump_outputs on a CPU workload: float32 files of the documented shapes; the cache rows are the ones at the LAST
+    timed step's slots (the table set that step used), the blocks are whole blocks that step wrote into."""
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, REPO)
+    import bench
+    from vllmini_amd.workload import DecodeConfig, make_workload
+
+    c = DecodeConfig("t", 70, 3, 64, 40, 512)         # 70 sequences: more than DUMP_BLOCKS, so the choice is a real one
+    wl = make_workload(c, "cpu", seed=3, table_sets=2, ragged=True)
+    assert len(wl.tables) == 2
+    k, v = wl.key.float(), wl.value.float()
+    out = torch.arange(c.batch * c.num_heads * c.head_size, dtype=torch.float16).view(c.batch, c.num_heads, c.head_size)
+    for steps, t in ((4, 1), (7, 0)):                 # the last of 4 steps used table set 1, the last of 7 set 0
+        kc0, vc0 = wl.key_cache.clone(), wl.value_cache.clone()
+        blk, off = wl.slots[t] // c.block_size, wl.slots[t] % c.block_size
+        for s in range(c.batch):                      # what reshape_and_cache leaves at that step's slots
+            wl.key_cache[blk[s], :, :, off[s], :] = wl.key[s].view(c.kv_heads, c.head_size // 8, 8)
+            wl.value_cache[blk[s], :, :, off[s]] = wl.value[s]
+        d = tmp_path / f"steps{steps}"
+        bench.dump_outputs(str(d), wl, out, steps)
+        got = {f[:-4]: np.load(d / f) for f in sorted(os.listdir(d))}
+        assert sorted(got) == ["key_cache_blocks", "key_cache_rows", "out", "value_cache_blocks", "value_cache_rows"]
+        assert all(a.dtype == np.float32 for a in got.values()) and sum(a.nbytes for a in got.values()) <= 64 << 20
+        assert np.array_equal(got["out"], out.float().numpy())
+        assert np.array_equal(got["key_cache_rows"], k.numpy()) and np.array_equal(got["value_cache_rows"], v.numpy())
+        assert got["key_cache_blocks"].shape == (bench.DUMP_BLOCKS, *wl.key_cache.shape[1:])
+        assert got["value_cache_blocks"].shape == (bench.DUMP_BLOCKS, *wl.value_cache.shape[1:])
+        written = {int(b) for b in blk}
+        hit = [int(b) for b in blk if np.array_equal(wl.value_cache[b].float().numpy(), got["value_cache_blocks"][0])]
+        assert hit and set(hit) <= written
+        wl.key_cache, wl.value_cache = kc0, vc0
