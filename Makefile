@@ -15,7 +15,7 @@ ARCH   ?= gfx950
 FLAGS  := --offload-arch=$(ARCH) -O3 -std=c++17 -ffp-contract=off -fPIC -fvisibility=hidden -fno-gpu-rdc -Iinclude
 CSRC   := vllmini_amd/csrc
 OUTDIR := vllmini_amd/_C
-CORE_UNITS := paged_attention pa_variants_extra pa_append_core pa_append_extra pa_variants_fp8 pa_queue pa_split
+CORE_UNITS := paged_attention pa_variants_extra pa_append_core pa_append_extra pa_variants_fp8 pa_queue pa_split pa_prefill
 ABSENT_UNITS := pa_extras_absent
 EXTRAS_UNITS := pa_variants_bf16 pa_append_bf16 pa_variants_fp8_bf16 pa_variants_fp8_e5m2 pa_variants_fp8_e5m2_bf16 \
           pa_variants_sparse pa_variants_sparse_bf16 pa_f32 pa_extras_cache pa_extras_abi

@@ -382,6 +382,35 @@ int vmi_paged_attention_v1_newest_f16(
     const void* key, const void* value, int64_t key_stride, int64_t value_stride, int32_t variant);
 
 /*
+ * Tiled causal attention of a CHUNK of query rows per sequence over the paged cache (extension; added under ABI 22 — a new
+ * entry changes nothing for existing callers, so the version stays): what a prefill needs, where the reference runs eager
+ * masked attention on the prompt (vllmini/model/gpt2.py:46-58, 71-78).  Kernel: vllmini_amd/csrc/pa_prefill.hpp.
+ *
+ *   cu_q_lens      [num_seqs + 1] int32: sequence s owns rows cu_q_lens[s] .. cu_q_lens[s+1]-1 of query / out (q_len rows)
+ *   seq_lens       [num_seqs] int32: tokens of the sequence in the cache, the chunk's own rows INCLUDED — the caller ran
+ *                  vmi_reshape_and_cache_f16 for them first.  Row j of the chunk sits at position seq_lens[s] - q_len + j and
+ *                  attends to positions 0 .. that of the blocks in block_tables[s].
+ *                  seq_lens[s] == q_len: a plain prefill; > q_len: a chunk over a cached context; q_len == 1: a decode row;
+ *                  q_len == 0 or seq_lens[s] == 0 (or lengths the tensors cannot hold): nothing is written for s.
+ *   out            [num_tokens, num_heads, head_size] fp16, contiguous (rows of no sequence are left alone)
+ *   query          [num_tokens, num_heads, head_size] fp16, row stride q_stride (may be 3*hidden)
+ *   block_tables   [num_seqs, max_num_blocks_per_seq] int32; entries >= ceil(seq_lens[s]/16) are never read
+ *   max_q_len      upper bound on the q_len of any sequence (sizes the grid; the lengths themselves stay on the device)
+ *   scale          multiplies the fp32 scores.  Scores and probabilities x V run on the matrix cores (fp16 operands, fp32
+ *                  sums), probabilities rounded to fp16: within 1.25e-3 absolute of an fp64 attention for |v| <= 1.
+ * Cache bytes past a row's causal range — the tail of the last block, blocks of table entries that are -1 — may hold anything,
+ * NaN patterns included: they are masked by selection.
+ * Supported: head_size in {64, 128}, block_size 16, x == 8, fp16 ("auto") pages, num_heads % num_kv_heads == 0.
+ * num_tokens == 0 or num_seqs == 0: returns 0 without a HIP call.
+ */
+int vmi_paged_attention_prefill_f16(
+    void* out, const void* query, const void* key_cache, const void* value_cache,
+    int32_t num_tokens, int32_t num_heads, int32_t head_size, int32_t num_kv_heads, float scale,
+    const int32_t* block_tables, const int32_t* seq_lens, const int32_t* cu_q_lens,
+    int32_t num_seqs, int32_t max_q_len, int32_t block_size, int32_t max_num_blocks_per_seq,
+    int64_t q_stride, int64_t kv_block_stride, int64_t kv_head_stride, int32_t device, void* stream);
+
+/*
  * The pool's preemption move (extension; counterpart of BlockManager.swap_to_cpu / swap_from_cpu,
  * vllmini/block_manager.py:70-87, which the reference runs as one copy per block, cache_kernels.cu:56-62): ONE launch on
  * `stream` moves block_mapping[i] = (src block, dst block) of BOTH caches for every i.

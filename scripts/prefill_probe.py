@@ -1,37 +1,88 @@
 #!/usr/bin/env python3
-"""prefill_batch: the causal attention through paged_attention_v1 (paged_prefill) against the eager masked attention.
-GPT-2 small, prompts U{4..512}; time per call and tokens/s, and the two paths' logits side by side."""
-import os, sys, time
+"""prefill_batch three ways on one build, alternated inside one process: the eager masked attention, the causal attention
+through paged_attention_v1 ("positions": paged_prefill) and the tiled MFMA kernel (prefill_attention="tiled").
+GPT-2 small, prompts U{4..512}; warm-up, then a host clock around a synchronise per call, medians; the paths' logits side by side.
+
+  prefill_probe.py [--reps R] [--out FILE.json]      the three-way timing for n in {1, 8, 32, 64}
+  prefill_probe.py --trace PATH [--n 64]             warm-up + 3 calls of ONE path (positions | tiled): run it under
+                                                     `rocprofv3 --kernel-trace --stats -- python scripts/prefill_probe.py --trace tiled`
+                                                     and read the attention kernel's time; prints the launch's operations
+                                                     (4 D sum(p + 1) per head) and unique K / V bytes per layer beside it."""
+import argparse, json, os, sys, time
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from vllmini_amd.gpt2_decode import GPT2Dims, GPT2PagedDecoder, random_state_dict
 from vllmini_amd.kv_pool import PagedKVPool
-from vllmini_amd import ops
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--reps", type=int, default=7)
+ap.add_argument("--out", default="")
+ap.add_argument("--trace", choices=["positions", "tiled"], default="")
+ap.add_argument("--n", type=int, default=64)
+args = ap.parse_args()
 
 dev = torch.device("cuda:0")
 dims = GPT2Dims()
 sd = random_state_dict(dims, dev)
+PATHS = {"eager": dict(paged_prefill=False), "positions": dict(), "tiled": dict(prefill_attention="tiled")}
+
+
+def make(n, kw):
+    pool = PagedKVPool(12 * 40 * n + 64, 12, 64, 16, 65, 12, device=dev, max_seqs=n)
+    return GPT2PagedDecoder(dims, sd, pool, **kw)
+
+
+def call(dec, n, prompts):
+    for s in range(n):
+        dec.pool.free(s)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    lg = dec.prefill_batch(list(range(n)), prompts)
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0, lg
+
+
+def shape_counts(prompts):
+    """Per layer, all heads: multiply-adds x 2 of QK^T and PV over the causal ranges, and the K / V bytes a launch must read once."""
+    H, D = dims.n_head, dims.head_size
+    pairs = sum(T * (T + 1) // 2 for T in map(len, prompts))          # sum over positions of (p + 1)
+    return 4 * D * pairs * H, 2 * sum(map(len, prompts)) * H * D * 2
+
+
 rng = np.random.default_rng(0)
-for n in (1, 8, 32, 64):
+records = []
+for n in ((args.n,) if args.trace else (1, 8, 32, 64)):
     prompts = [rng.integers(0, dims.vocab_size, int(rng.integers(4, 513))).tolist() for _ in range(n)]
-    res = {}
-    for paged in (False, True):
-        pool = PagedKVPool(12 * 40 * n + 64, 12, 64, 16, 65, 12, device=dev, max_seqs=n)
-        dec = GPT2PagedDecoder(dims, sd, pool, paged_prefill=paged)
-        ts = []
-        for rep in range(4):
-            for s in range(n):
-                pool.free(s)
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            lg = dec.prefill_batch(list(range(n)), prompts)
-            torch.cuda.synchronize()
-            ts.append(time.perf_counter() - t0)
-        res[paged] = (min(ts[1:]), lg.float().cpu())
-        label = ops.variant_names()[ops.last_variant() - 1] if paged else "-"
-        del dec, pool
     tok = sum(len(p) for p in prompts)
-    d = (res[True][1] - res[False][1]).abs().max().item()
-    same = (res[True][1].argmax(-1) == res[False][1].argmax(-1)).float().mean().item()
-    print(f"n={n:3d} tokens={tok:6d} eager {res[False][0]*1e3:8.2f} ms ({tok/res[False][0]/1e3:7.1f} k tok/s)  paged {res[True][0]*1e3:8.2f} ms "
-          f"({tok/res[True][0]/1e3:7.1f} k tok/s)  kernel {label}  max|dlogit| {d:.3e} (|logit| max {res[False][1].abs().max():.2f}) argmax agree {same:.3f}", flush=True)
+    flops, kv_bytes = shape_counts(prompts)
+    if args.trace:
+        dec = make(n, PATHS[args.trace])
+        for _ in range(4):
+            call(dec, n, prompts)
+        print(f"trace {args.trace}: n={n} tokens={tok} layers={dims.n_layer}; per attention launch {flops/1e9:.3f} GFLOP, "
+              f"unique K/V {kv_bytes/1e6:.2f} MB", flush=True)
+        continue
+    decs = {name: make(n, kw) for name, kw in PATHS.items()}
+    ts, logits = {name: [] for name in decs}, {}
+    for rep in range(args.reps + 1):                                    # rep 0 is the warm-up
+        for name, dec in decs.items():                                  # alternated: a drift of the machine hits all three
+            t, lg = call(dec, n, prompts)
+            if rep:
+                ts[name].append(t)
+            logits[name] = lg.float().cpu()
+    med = {name: float(np.median(v)) for name, v in ts.items()}
+    spread = {name: (float(np.min(v)), float(np.max(v))) for name, v in ts.items()}
+    d = {name: (logits[name] - logits["eager"]).abs().max().item() for name in ("positions", "tiled")}
+    same = (logits["tiled"].argmax(-1) == logits["positions"].argmax(-1)).float().mean().item()
+    records.append({"n": n, "tokens": tok, "median_ms": {k: v * 1e3 for k, v in med.items()},
+                    "min_max_ms": {k: [a * 1e3, b * 1e3] for k, (a, b) in spread.items()},
+                    "max_dlogit_vs_eager": d, "argmax_agree_tiled_positions": same,
+                    "attention_gflop_per_layer": flops / 1e9, "unique_kv_mb_per_layer": kv_bytes / 1e6})
+    print(f"n={n:3d} tokens={tok:6d}  " + "  ".join(f"{k} {med[k]*1e3:8.2f} ms ({tok/med[k]/1e3:7.1f} k tok/s)" for k in med) +
+          f"  max|dlogit| vs eager: positions {d['positions']:.3e} tiled {d['tiled']:.3e}  argmax tiled==positions {same:.3f}", flush=True)
+    del decs
+    torch.cuda.empty_cache()
+if args.out and records:
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(records, f, indent=1)

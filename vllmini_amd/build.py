@@ -8,7 +8,8 @@ native code at all: hipcc translation units compiled concurrently and linked int
                                                     vllmini_amd/_lib.py): the hot path of SURVEY.md §8 and nothing else —
                                                     float16 tensors over float16 or fp8-E4M3 pages (every head / block
                                                     size of the reference's dispatch, grouped-query heads, ALiBi,
-                                                    paged_attention_v2, the fused append, copy/swap_blocks).  Seven units.
+                                                    paged_attention_v2, the fused append, copy/swap_blocks) and the tiled
+                                                    causal prefill attention (pa_prefill.hip).  Eight units + the stub below.
                                                     No diagnostic entry, no kernel that is wrong by design, no experiment
                                                     kernel, and none of the out-of-scope element types and operators: their
                                                     kernel menus are EMPTY here (pa_extras_absent.hip, chosen at link time)
@@ -54,12 +55,13 @@ SRC_FP8_E5M2 = [os.path.join(CSRC, f"pa_variants_fp8_e5m2{t}.hip") for t in ("",
 SRC_F32 = os.path.join(CSRC, "pa_f32.hip")                    # float32 tensors (x = 4)
 SRC_QUEUE = os.path.join(CSRC, "pa_queue.hip")                # balanced (work-queue) kernels for ragged batches
 SRC_SPLIT = os.path.join(CSRC, "pa_split.hip")                # split kernels: one (sequence, head) over several workgroups + workspace
+SRC_PREFILL = os.path.join(CSRC, "pa_prefill.hip")            # tiled causal prefill attention over the paged cache (MFMA)
 SRC_STAGE = os.path.join(CSRC, "pa_stage.hip")                # experiment: pages staged through LDS (diagnostic library only)
 SRC_ABSENT = os.path.join(CSRC, "pa_extras_absent.hip")      # product library: empty out-of-scope menus, no out-of-scope entry
 SRC_EXTRAS_CACHE = os.path.join(CSRC, "pa_extras_cache.hip")  # extras: convert_fp8, reshape_and_cache_flash, bf16 / E5M2 fp8 scatter
 SRC_EXTRAS_ABI = os.path.join(CSRC, "pa_extras_abi.hip")      # extras: the C-ABI entries of include/vmi_paged_attention_extras.h
 # (source, flavor): flavor "" = plain, "extras" = -DVMI_EXTRAS, "diag" = -DVMI_DIAG (+ -DVMI_EXTRAS)
-CORE = [SRC, SRC_EXTRA, SRC_APPEND[0], SRC_APPEND[1], SRC_FP8, SRC_QUEUE, SRC_SPLIT]          # the hot path
+CORE = [SRC, SRC_EXTRA, SRC_APPEND[0], SRC_APPEND[1], SRC_FP8, SRC_QUEUE, SRC_SPLIT, SRC_PREFILL]   # the hot path
 EXTRAS = [SRC_BF16, SRC_APPEND[2], SRC_FP8_BF16, *SRC_FP8_E5M2, *SRC_SPARSE, SRC_F32, SRC_EXTRAS_CACHE, SRC_EXTRAS_ABI]
 PRODUCT_UNITS = [(s, "") for s in CORE] + [(SRC_ABSENT, "")]
 EXTRAS_UNITS = [(s, "extras" if s == SRC_QUEUE else "") for s in CORE] + [(s, "") for s in EXTRAS]
@@ -72,6 +74,7 @@ SOURCES = [*CORE, SRC_ABSENT, *EXTRAS]                        # every unit of th
 HDR = os.path.join(CSRC, "pa_kernel.hpp")
 HDR_QUEUE = os.path.join(CSRC, "pa_queue.hpp")
 HDR_SPLIT = os.path.join(CSRC, "pa_split.hpp")
+HDR_PREFILL = os.path.join(CSRC, "pa_prefill.hpp")
 HDRS_HOST = [os.path.join(CSRC, "pa_host.hpp"), os.path.join(CSRC, "pa_cache_fp8.hpp")]
 INCLUDE = os.path.join(REPO_ROOT, "include")
 OUT_DIR = os.path.join(PKG_DIR, "_C")
@@ -115,7 +118,7 @@ def _units_of(kind: str):
 
 
 def _deps(kind: str = "product") -> list[str]:
-    return [*(s for s, _ in _units_of(kind)), *TABLES, HDR, HDR_QUEUE, HDR_SPLIT, *HDRS_HOST,
+    return [*(s for s, _ in _units_of(kind)), *TABLES, HDR, HDR_QUEUE, HDR_SPLIT, HDR_PREFILL, *HDRS_HOST,
             os.path.join(INCLUDE, "vmi_paged_attention.h"), os.path.join(INCLUDE, "vmi_paged_attention_extras.h"),
             os.path.join(INCLUDE, "vmi_paged_attention_diag.h"),
             os.path.abspath(__file__)]

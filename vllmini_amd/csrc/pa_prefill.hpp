@@ -1,0 +1,211 @@
+// pa_prefill.hpp — tiled causal attention of a CHUNK of query rows per sequence over the paged KV cache (prefill, chunked
+// prefill, and — with one row — decode), on the matrix cores.  fp16 query / out, fp16 pages, block size 16, x = 8, head size
+// 64 or 128.  Launcher and C-ABI entry: pa_prefill.hip.
+//
+// Operator: sequence s owns query rows cu_q_lens[s] .. cu_q_lens[s+1]-1 (q_len of them); row j sits at position
+// p = seq_lens[s] - q_len + j and attends to cache positions 0..p of the blocks in block_tables[s].  All seq_lens[s] K / V
+// rows are in the cache before the launch.
+//
+// Work split.  A wave owns a 16-row query tile of one (sequence, head); a workgroup is four waves = 64 consecutive rows.
+// The four tiles start together and walk the same K / V blocks from block 0 upwards, two blocks per trip, each straight
+// from global memory into MFMA operand registers — a block fetched by one wave is an L1 / L2 hit for the other three (no
+// LDS, no barrier: the tiles' trip counts differ by at most two, and a wave past its diagonal simply leaves).
+//
+// Arithmetic per trip (a PAIR of 16-token blocks), everything transposed so that no operand ever changes lanes:
+//   S^T = K . Q^T    v_mfma_f32_16x16x32_f16, A = the K block exactly as it lies in the page ([D/8][16][8] halves: lane
+//                    l = 16*kg + token reads 16 bytes at 1 KiB * chunk + 16 * l — one contiguous KiB per instruction),
+//                    B = Q^T held in registers for the whole kernel (lane: query row l & 15, dims 32*chunk + 8*kg ..+7).
+//                    The C layout leaves lane (n = l & 15, kg = l >> 4) with tokens 4*kg .. 4*kg+3 of query column n.
+//   online softmax   per query COLUMN: the column's values live in the four lanes {n, n+16, n+32, n+48}, so the block
+//                    maximum is two cross-lane steps (xor 16, xor 32); running max / sum / rescale in fp32; `scale`
+//                    (times log2 e) multiplies the fp32 scores; the causal mask SELECTS -inf.
+//   O^T += V^T . P^T v_mfma_f32_16x16x32_f16 over the pair: k index 8*kg + j = token 4*kg + j of the first block (j < 4) or
+//                    4*kg + j - 4 of the second — for B that is the lane's own eight probabilities (rounded to fp16, the
+//                    sum is taken over the ROUNDED values), for A = V^T two 8-byte pieces of the V page [D][16] (row
+//                    16*t + n, tokens 4*kg ..): sixteen rows = one contiguous 512 B per instruction.
+//                    The accumulator's column is again query n: the column's rescale factor applies to the lane's own
+//                    registers, and the final 1 / sum as well.
+// V elements of tokens past the tile's last position (the tail of the last block, the absent second block of an odd pair)
+// are cleared by a bit mask before they meet a zero probability: the bytes there may be NaN patterns.  Tokens between a
+// row's position and the tile's last position are rows the caller wrote (positions < seq_len) and meet p = 0.
+// Blocks wholly above the tile's diagonal are never loaded; block-table entries past them are never read.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+
+namespace vmi {
+namespace prefill {
+
+typedef _Float16 h16;
+typedef _Float16 h16x4 __attribute__((ext_vector_type(4)));
+typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int BS = 16;          // tokens per block
+constexpr int TILE = 16;        // query rows per wave
+constexpr int WAVES = 4;        // tiles per workgroup
+constexpr int ROWS = TILE * WAVES;
+
+struct Params {
+  h16* out;                     // [num_tokens, num_heads, D]
+  const h16* q;                 // rows of stride q_stride
+  const h16* kc;                // [blocks, kv_heads, D/8, 16, 8]
+  const h16* vc;                // [blocks, kv_heads, D, 16]
+  const int32_t* block_tables;  // [num_seqs, max_blocks_per_seq]
+  const int32_t* seq_lens;      // [num_seqs]
+  const int32_t* cu_q_lens;     // [num_seqs + 1]
+  int64_t q_stride, kv_block_stride, kv_head_stride;
+  int32_t num_tokens, num_heads, q_per_kv, num_seqs, max_blocks_per_seq;
+  float scale_log2e;            // scale * log2(e): the softmax runs on exp2
+};
+
+// Grid: one workgroup per (64-row group, sequence, head), x = group_rev * (num_seqs * num_heads) + seq * num_heads + head.
+// group_rev counts a sequence's groups from its LAST one, so the first num_seqs * num_heads workgroups of the launch are
+// every sequence's longest causal range; a sequence with fewer groups than the host bound leaves the surplus at once.
+template <int D>
+__global__ void __launch_bounds__(WAVES * 64) pa_prefill_kernel(const Params p) {
+  constexpr int KC = D / 32;    // 32-dim chunks of a K block: one MFMA each
+  constexpr int VT = D / 16;    // 16-dim tiles of the output: one MFMA each
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int items = p.num_seqs * p.num_heads;
+  const int grev = blockIdx.x / items;
+  const int rem = blockIdx.x - grev * items;
+  const int seq = rem / p.num_heads, head = rem - seq * p.num_heads;
+  const int row_lo = p.cu_q_lens[seq], row_hi = p.cu_q_lens[seq + 1];
+  const int q_len = row_hi - row_lo, L = p.seq_lens[seq];
+  const int ctx = L - q_len;    // cached positions in front of the chunk
+  // nothing to do, or lengths the tensors cannot hold: the sequence writes nothing
+  if (q_len <= 0 || L <= 0 || ctx < 0 || row_lo < 0 || row_hi > p.num_tokens || (L + BS - 1) / BS > p.max_blocks_per_seq)
+    return;
+  const int ngroups = (q_len + ROWS - 1) / ROWS;
+  if (grev >= ngroups) return;
+  const int j0 = ((ngroups - 1 - grev) * WAVES + wave) * TILE;   // first row of my tile within the chunk
+  if (j0 >= q_len) return;                                        // (wave-uniform)
+
+  const int n = lane & 15, kg = lane >> 4;
+  const int jr = min(j0 + n, q_len - 1);                 // rows past the chunk repeat its last row and are not stored
+  const int pos = ctx + jr;                              // my column's position: it attends to tokens 0..pos
+  const int last_pos = ctx + min(j0 + TILE - 1, q_len - 1);
+  const int nblk = last_pos / BS + 1, npair = (nblk + 1) >> 1;
+
+  const h16* qp = p.q + (int64_t)(row_lo + jr) * p.q_stride + (int64_t)head * D + 8 * kg;
+  h16x8 qB[KC];
+#pragma unroll
+  for (int c = 0; c < KC; ++c) qB[c] = *reinterpret_cast<const h16x8*>(qp + 32 * c);
+
+  const int64_t head_off = (int64_t)(head / p.q_per_kv) * p.kv_head_stride;
+  const h16* kbase = p.kc + head_off + 8 * lane;
+  const h16* vbase = p.vc + head_off + n * BS + 4 * kg;
+  const int32_t* bt = p.block_tables + (int64_t)seq * p.max_blocks_per_seq;
+
+  // a pair's physical blocks; the absent second block of an odd count re-reads the first (its tokens are masked)
+  auto phys_of = [&](int pp, int i) -> int64_t {
+    const int b = min(2 * pp + i, nblk - 1);
+    return (int64_t)__builtin_amdgcn_readfirstlane(bt[b]) * p.kv_block_stride;
+  };
+  auto load_k = [&](h16x8(&k)[2][KC], int pp) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const h16* blk = kbase + phys_of(pp, i);
+#pragma unroll
+      for (int c = 0; c < KC; ++c) k[i][c] = *reinterpret_cast<const h16x8*>(blk + 512 * c);
+    }
+  };
+  auto load_v = [&](u32x2(&v)[2][VT], int pp) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const h16* blk = vbase + phys_of(pp, i);
+#pragma unroll
+      for (int t = 0; t < VT; ++t) v[i][t] = *reinterpret_cast<const u32x2*>(blk + 16 * BS * t);
+    }
+  };
+
+  f32x4 o[VT];
+#pragma unroll
+  for (int t = 0; t < VT; ++t) o[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+  float m = -3.0e38f, lsum = 0.f;     // running max (log2 domain) and this lane's share of the running sum
+
+  h16x8 kcur[2][KC], knext[2][KC];
+  u32x2 v[2][VT];
+  load_k(kcur, 0);
+  for (int pp = 0; pp < npair; ++pp) {
+    load_v(v, pp);
+    load_k(knext, min(pp + 1, npair - 1));   // (the last trip re-reads its own pair: no branch around the loads)
+
+    // ---- S^T = K . Q^T, scaled in fp32, causal mask selected ----
+    float s[2][4];
+    float mx = -INFINITY;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int c = 0; c < KC; ++c) acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(kcur[i][c], qB[c], acc, 0, 0, 0);
+      const int tok0 = (2 * pp + i) * BS + 4 * kg;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        s[i][r] = (tok0 + r <= pos) ? acc[r] * p.scale_log2e : -INFINITY;
+        mx = fmaxf(mx, s[i][r]);
+      }
+    }
+    mx = fmaxf(mx, __shfl_xor(mx, 16));
+    mx = fmaxf(mx, __shfl_xor(mx, 32));
+    const float m_new = fmaxf(m, mx);
+    const float alpha = __builtin_amdgcn_exp2f(m - m_new);
+    m = m_new;
+    h16x8 pB;
+    float psum = 0.f;
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const h16 ph = (h16)__builtin_amdgcn_exp2f(s[i][r] - m_new);
+        pB[4 * i + r] = ph;
+        psum += (float)ph;
+      }
+    lsum = lsum * alpha + psum;
+    if (__any(alpha != 1.f)) {
+#pragma unroll
+      for (int t = 0; t < VT; ++t) o[t] *= alpha;
+    }
+
+    // ---- O^T += V^T . P^T ----
+    if (pp == npair - 1) {   // the only trip that can hold tokens past the tile's last position: clear them
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        const int nv = last_pos + 1 - ((2 * pp + i) * BS + 4 * kg);   // valid tokens of my four
+        const u32x2 keep = {nv >= 2 ? 0xffffffffu : nv == 1 ? 0xffffu : 0u, nv >= 4 ? 0xffffffffu : nv == 3 ? 0xffffu : 0u};
+#pragma unroll
+        for (int t = 0; t < VT; ++t) v[i][t] &= keep;
+      }
+    }
+#pragma unroll
+    for (int t = 0; t < VT; ++t) {
+      const u32x4 va = {v[0][t][0], v[0][t][1], v[1][t][0], v[1][t][1]};
+      o[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h16x8, va), pB, o[t], 0, 0, 0);
+    }
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int c = 0; c < KC; ++c) kcur[i][c] = knext[i][c];
+  }
+
+  lsum += __shfl_xor(lsum, 16);
+  lsum += __shfl_xor(lsum, 32);
+  if (j0 + n < q_len) {
+    const float inv = 1.f / lsum;   // (a stored row attends at least to token 0 and its maximum contributes exp2(0): lsum >= 1)
+    h16* op = p.out + ((int64_t)(row_lo + j0 + n) * p.num_heads + head) * D + 4 * kg;
+#pragma unroll
+    for (int t = 0; t < VT; ++t) {
+      const h16x4 h = {(h16)(o[t][0] * inv), (h16)(o[t][1] * inv), (h16)(o[t][2] * inv), (h16)(o[t][3] * inv)};
+      *reinterpret_cast<h16x4*>(op + 16 * t) = h;
+    }
+  }
+}
+
+}  // namespace prefill
+}  // namespace vmi

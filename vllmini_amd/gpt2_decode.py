@@ -89,7 +89,7 @@ class GPT2PagedDecoder:
     def __init__(self, dims: GPT2Dims, state_dict: Dict[str, torch.Tensor], pool: PagedKVPool,
                  reference_off_by_one: bool = False, fused_append: bool = False, native_layers: Optional[bool] = None,
                  scatter_in_c_attn: Optional[bool] = None, deferred_scatter: bool = False, pad_batch_to: int = 0,
-                 paged_prefill: Optional[bool] = None):
+                 paged_prefill: Optional[bool] = None, prefill_attention: str = "positions"):
         assert pool.num_layers == dims.n_layer and pool.num_heads == dims.n_head
         assert pool.head_size == dims.head_size
         self.dims, self.sd, self.pool = dims, state_dict, pool
@@ -157,6 +157,18 @@ class GPT2PagedDecoder:
         # cache — instead of the reference's eager masked attention (gpt2.py:46-58): one launch per layer for all prompts of
         # the call, and prefill logits with the decode path's own arithmetic.  None = on a HIP device; False = eager.
         self.paged_prefill = (pool.device.type == "cuda") if paged_prefill is None else bool(paged_prefill)
+        # prefill_attention: how prefill_batch runs the prompts' causal attention.  "positions" = the code above (paged_prefill /
+        # eager).  "tiled" = ONE ops.paged_attention_prefill launch per layer over the packed prompts: 16-row query tiles on the
+        # matrix cores, every K / V block of a prompt read once per 64 rows instead of once per position, per-SEQUENCE tables
+        # (no [layers, sum T, blocks] gather).  Opt-in: the two round differently (fp16 probabilities into an fp32 MFMA sum
+        # against the decode kernel's fp16 products).
+        if prefill_attention not in ("positions", "tiled"):
+            raise ValueError(f"prefill_attention must be 'positions' or 'tiled', got {prefill_attention!r}")
+        if prefill_attention == "tiled" and (pool.kv_cache_dtype != "auto" or wdt != torch.float16 or pool.block_size != 16 or
+                                             dims.head_size not in (64, 128)):
+            raise ValueError("prefill_attention='tiled' is built for float16 weights and pages, head size 64 / 128 and block size 16; "
+                             f"got {wdt}, kv_cache_dtype='{pool.kv_cache_dtype}', head size {dims.head_size}, block size {pool.block_size}")
+        self.prefill_attention = prefill_attention
         self.pad_batch_to = int(pad_batch_to)      # decode steps are laid out for the next multiple of this many rows (0: as they come)
 
     # ---- pieces shared by prefill and decode --------------------------------------------------------
@@ -235,7 +247,13 @@ class GPT2PagedDecoder:
         starts = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
         pos = torch.from_numpy(np.concatenate([np.arange(T, dtype=np.int64) for T in lens])).to(dev)
         x = self.sd["transformer.wte.weight"][ids] + self.sd["transformer.wpe.weight"][pos]
-        paged = self.paged_prefill
+        tiled = self.prefill_attention == "tiled"
+        paged = self.paged_prefill and not tiled
+        if tiled:
+            mbe = -(-max(lens) // pool.block_size)
+            tables_seq = torch.from_numpy(np.ascontiguousarray(np.stack(tabs, axis=1)[:, :, :mbe])).to(dev)   # [layers, n, mbe]
+            lens_seq = torch.as_tensor(lens, dtype=torch.int32).to(dev)
+            cu_q = torch.from_numpy(starts.astype(np.int32)).to(dev)
         if paged:
             mbe = -(-max(lens) // pool.block_size)
             seq_of_tok = torch.from_numpy(np.repeat(np.arange(n, dtype=np.int64), lens)).to(dev)
@@ -254,7 +272,7 @@ class GPT2PagedDecoder:
             cur_T = T
         groups.append(cur)
         plans = []
-        for g in ([] if paged else groups):
+        for g in ([] if paged or tiled else groups):
             T = max(lens[i] for i in g)
             idx = np.zeros((len(g), T), dtype=np.int64)                      # packed row of (prompt, position); pads -> row 0
             valid = np.zeros((len(g), T), dtype=bool)
@@ -269,6 +287,9 @@ class GPT2PagedDecoder:
             q, k, v = self._qkv(self._ln(x, p + "ln_1"), p)                                       # [sum T, H, D] views
             cache_ops.reshape_and_cache(k, v, pool.key_cache, pool.value_cache, slots_dev[i], pool.kv_cache_dtype, pool.kv_scale)
             a = torch.empty((x.shape[0], E), dtype=x.dtype, device=dev)
+            if tiled:
+                ops.paged_attention_prefill(a.view(-1, H, D), q, pool.key_cache, pool.value_cache, H, self.scale, tables_seq[i],
+                                            lens_seq, cu_q, max(lens), pool.block_size)
             if paged:
                 ops.paged_attention_v1(a.view(-1, H, D), q, pool.key_cache, pool.value_cache, H, self.scale, tables_tok[i], lens_tok,
                                        pool.block_size, mbe * pool.block_size, None, pool.kv_cache_dtype, pool.kv_scale, 0, 0, 1, 1, 0,

@@ -32,6 +32,7 @@ from . import _lib
 __all__ = [
     "paged_attention_v1",
     "paged_attention_v2",
+    "paged_attention_prefill",
     "reshape_and_cache",
     "pick_variant",
     "workspace_for",
@@ -465,6 +466,93 @@ def paged_attention_v2(
         fn = _extras("paged_attention_v2 over bfloat16 tensors").vmi_paged_attention_v2_bf16 if query.dtype == torch.bfloat16 else \
             _lib.load().vmi_paged_attention_v2_f16
         rc = fn(args[0], exp_sums.data_ptr(), max_logits.data_ptr(), tmp_out.data_ptr(), *args[1:], int(_variant))
+    if rc != 0:
+        _raise_native(rc)
+    return None
+
+
+def paged_attention_prefill(
+    out: torch.Tensor,
+    query: torch.Tensor,
+    key_cache: torch.Tensor,
+    value_cache: torch.Tensor,
+    num_kv_heads: int,
+    scale: float,
+    block_tables: torch.Tensor,
+    seq_lens: torch.Tensor,
+    cu_q_lens: torch.Tensor,
+    max_q_len: int,
+    block_size: int,
+) -> None:
+    """Tiled causal attention of a chunk of query rows per sequence over the paged cache (extension: the reference runs its
+    prefill as eager masked attention, gpt2.py:46-58); writes `out` in place, returns None.
+
+    query / out [num_tokens, num_heads, head_size] float16 (query rows may be strided: the fused projection's views);
+    sequence s owns rows cu_q_lens[s] .. cu_q_lens[s+1]-1, which sit at positions seq_lens[s] - q_len .. seq_lens[s] - 1 of the
+    blocks in block_tables[s] — their K / V rows are in the cache already (reshape_and_cache first).  seq_lens[s] == q_len is
+    a plain prefill, > q_len a chunk over a cached context.  `max_q_len` bounds the q_len of every sequence (host-known: it
+    sizes the grid).  float16 pages, head size 64 / 128, block size 16 (include/vmi_paged_attention.h)."""
+    qs = query.shape
+    if len(qs) != 3:
+        raise RuntimeError(f"query must be [num_tokens, num_heads, head_size], got {tuple(qs)}")
+    if query.dtype != torch.float16:
+        raise RuntimeError(f"Unsupported input type of paged attention prefill: {query.dtype} (float16 is built)")
+    index = query.get_device()
+    dev = query.device
+    if index < 0:
+        _check_device("query", query, dev)
+    _on("out", out, index, dev)
+    _on("key_cache", key_cache, index, dev)
+    _on("value_cache", value_cache, index, dev)
+    _on("block_tables", block_tables, index, dev)
+    _on("seq_lens", seq_lens, index, dev)
+    _on("cu_q_lens", cu_q_lens, index, dev)
+    if key_cache.dtype != torch.float16 or value_cache.dtype != torch.float16:
+        raise RuntimeError("key_cache/value_cache must be torch.float16 (paged_attention_prefill is built for kv_cache_dtype='auto')")
+    if out.dtype != torch.float16:
+        raise RuntimeError(f"out must be torch.float16, got {out.dtype}")
+    if block_tables.dtype != torch.int32 or seq_lens.dtype != torch.int32 or cu_q_lens.dtype != torch.int32:
+        raise RuntimeError("block_tables, seq_lens and cu_q_lens must be int32")
+    num_tokens, num_heads, head_size = qs
+    ks, vs = key_cache.shape, value_cache.shape
+    if len(ks) != 5 or len(vs) != 4:
+        raise RuntimeError("key_cache must be [num_blocks, num_kv_heads, head_size/x, block_size, x] "
+                           "and value_cache [num_blocks, num_kv_heads, head_size, block_size]")
+    if ks[4] != 8:
+        raise RuntimeError(f"key_cache innermost dimension must be 8 (16 bytes per chunk), got {ks[4]}")
+    block_size = int(block_size)
+    if ks[3] != block_size or vs[3] != block_size:
+        raise RuntimeError(f"block_size={block_size} does not match the cache tensors ({ks[3]}, {vs[3]})")
+    if ks[2] * 8 != head_size or vs[2] != head_size:
+        raise RuntimeError("cache head_size does not match query head_size")
+    num_kv_heads = int(num_kv_heads)
+    if ks[1] != num_kv_heads or vs[1] != num_kv_heads:
+        raise RuntimeError("cache num_kv_heads does not match num_kv_heads argument")
+    qst = query.stride()
+    if qst[2] != 1 or qst[1] != head_size:
+        raise RuntimeError("query must be contiguous in its last two dimensions")
+    kst, vst = key_cache.stride(), value_cache.stride()
+    tile = head_size * block_size
+    if kst[4] != 1 or kst[3] != 8 or kst[2] != block_size * 8 or (kst[1] != tile and ks[1] != 1) or vst[3] != 1 or \
+            vst[2] != block_size or (vst[1] != tile and vs[1] != 1):
+        raise RuntimeError("each cache block must be dense")
+    if vst[0] != kst[0] or vst[1] != kst[1]:
+        raise RuntimeError("key_cache and value_cache must have identical block/head strides")
+    if not out.is_contiguous() or out.numel() != num_tokens * num_heads * head_size:
+        raise RuntimeError("out must be contiguous with num_tokens*num_heads*head_size elements")
+    ts, tst = block_tables.shape, block_tables.stride()
+    num_seqs = seq_lens.shape[0] if seq_lens.dim() == 1 else -1
+    if num_seqs < 0 or not seq_lens.is_contiguous():
+        raise RuntimeError("seq_lens must be a contiguous [num_seqs] tensor")
+    if len(ts) != 2 or ts[0] != num_seqs or tst[1] != 1 or (tst[0] != ts[1] and num_seqs > 1):
+        raise RuntimeError("block_tables must be a row-contiguous [num_seqs, max_num_blocks_per_seq] tensor")
+    if cu_q_lens.dim() != 1 or cu_q_lens.shape[0] != num_seqs + 1 or not cu_q_lens.is_contiguous():
+        raise RuntimeError("cu_q_lens must be a contiguous [num_seqs + 1] tensor")
+    rc = _lib.load().vmi_paged_attention_prefill_f16(
+        out.data_ptr(), query.data_ptr(), key_cache.data_ptr(), value_cache.data_ptr(),
+        num_tokens, num_heads, head_size, num_kv_heads, float(scale),
+        block_tables.data_ptr(), seq_lens.data_ptr(), cu_q_lens.data_ptr(),
+        num_seqs, int(max_q_len), block_size, ts[1], qst[0], kst[0], kst[1], index, _stream_of(index))
     if rc != 0:
         _raise_native(rc)
     return None
