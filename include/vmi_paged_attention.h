@@ -411,6 +411,25 @@ int vmi_paged_attention_prefill_f16(
     int64_t q_stride, int64_t kv_block_stride, int64_t kv_head_stride, int32_t device, void* stream);
 
 /*
+ * The same operator over fp8-E4M3 pages (kv_cache_dtype "fp8" / "fp8_e4m3"; added under ABI 22 like the entry above).
+ * Arguments, lengths, masking and validation are vmi_paged_attention_prefill_f16's; what differs:
+ *   key_cache      [num_blocks, num_kv_heads, head_size/16, 16, 16] E4M3 bytes, value_cache [num_blocks, num_kv_heads,
+ *                  head_size, 16] — what vmi_reshape_and_cache_fp8 writes (x == 16); an element means fp8 * kv_scale.
+ *                  16-byte aligned; kv_block_stride / kv_head_stride are in cache elements (bytes) and multiples of 16.
+ *   kv_scale       finite and positive, else VMI_E_SHAPE.  It is folded into the fp32 score scale (K) and the final
+ *                  kv_scale / sum (V): kv_scale == 1 computes exactly what no scale would.
+ * The bytes are decoded to fp16 in registers (lossless: every E4M3 value is an fp16 value) and meet fp16 q / probabilities on
+ * the matrix cores: within 1.25e-3 * kv_scale * max|decoded v| of an fp64 attention over the decoded pages.  Stale bytes past
+ * a row's causal range may hold anything, the NaN code 0x7F included.  Kernel: vllmini_amd/csrc/pa_prefill_fp8.hpp.
+ */
+int vmi_paged_attention_prefill_fp8(
+    void* out, const void* query, const void* key_cache, const void* value_cache,
+    int32_t num_tokens, int32_t num_heads, int32_t head_size, int32_t num_kv_heads, float scale,
+    const int32_t* block_tables, const int32_t* seq_lens, const int32_t* cu_q_lens,
+    int32_t num_seqs, int32_t max_q_len, int32_t block_size, int32_t max_num_blocks_per_seq,
+    int64_t q_stride, int64_t kv_block_stride, int64_t kv_head_stride, int32_t device, void* stream, float kv_scale);
+
+/*
  * The pool's preemption move (extension; counterpart of BlockManager.swap_to_cpu / swap_from_cpu,
  * vllmini/block_manager.py:70-87, which the reference runs as one copy per block, cache_kernels.cu:56-62): ONE launch on
  * `stream` moves block_mapping[i] = (src block, dst block) of BOTH caches for every i.

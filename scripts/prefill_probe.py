@@ -1,10 +1,12 @@
 #!/usr/bin/env python3
 """prefill_batch three ways on one build, alternated inside one process: the eager masked attention, the causal attention
-through paged_attention_v1 ("positions": paged_prefill) and the tiled MFMA kernel (prefill_attention="tiled").
+through paged_attention_v1 ("positions": paged_prefill) and the tiled MFMA kernel (prefill_attention="tiled"; over an fp8 pool,
+--kv-cache-dtype fp8, the third path is prefill_attention="auto", which resolves to the fp8 tiled kernel).
 GPT-2 small, prompts U{4..512}; warm-up, then a host clock around a synchronise per call, medians; the paths' logits side by side.
 
   prefill_probe.py [--reps R] [--out FILE.json]      the three-way timing for n in {1, 8, 32, 64}
-  prefill_probe.py --trace PATH [--n 64]             warm-up + 3 calls of ONE path (positions | tiled): run it under
+  prefill_probe.py --trace PATH [--n 64]             warm-up + 3 calls of ONE path (positions | tiled | auto, printed as what it
+                                                     resolved to): run it under
                                                      `rocprofv3 --kernel-trace --stats -- python scripts/prefill_probe.py --trace tiled`
                                                      and read the attention kernel's time; prints the launch's operations
                                                      (4 D sum(p + 1) per head) and unique K / V bytes per layer beside it."""
@@ -17,18 +19,23 @@ from vllmini_amd.kv_pool import PagedKVPool
 ap = argparse.ArgumentParser()
 ap.add_argument("--reps", type=int, default=7)
 ap.add_argument("--out", default="")
-ap.add_argument("--trace", choices=["positions", "tiled"], default="")
+ap.add_argument("--trace", choices=["positions", "tiled", "auto"], default="")
 ap.add_argument("--n", type=int, default=64)
+ap.add_argument("--kv-cache-dtype", choices=["auto", "fp8"], default="auto")
 args = ap.parse_args()
 
 dev = torch.device("cuda:0")
 dims = GPT2Dims()
 sd = random_state_dict(dims, dev)
-PATHS = {"eager": dict(paged_prefill=False), "positions": dict(), "tiled": dict(prefill_attention="tiled")}
+FP8 = args.kv_cache_dtype == "fp8"
+TILED = "auto" if FP8 else "tiled"              # the third path's name: "tiled" refuses fp8 pools, "auto" resolves to their kernel
+PATHS = {"eager": dict(paged_prefill=False), "positions": dict(), TILED: dict(prefill_attention=TILED)}
+if args.trace:
+    PATHS.setdefault(args.trace, dict(prefill_attention=args.trace))
 
 
 def make(n, kw):
-    pool = PagedKVPool(12 * 40 * n + 64, 12, 64, 16, 65, 12, device=dev, max_seqs=n)
+    pool = PagedKVPool(12 * 40 * n + 64, 12, 64, 16, 65, 12, device=dev, max_seqs=n, kv_cache_dtype=args.kv_cache_dtype)
     return GPT2PagedDecoder(dims, sd, pool, **kw)
 
 
@@ -46,7 +53,7 @@ def shape_counts(prompts):
     """Per layer, all heads: multiply-adds x 2 of QK^T and PV over the causal ranges, and the K / V bytes a launch must read once."""
     H, D = dims.n_head, dims.head_size
     pairs = sum(T * (T + 1) // 2 for T in map(len, prompts))          # sum over positions of (p + 1)
-    return 4 * D * pairs * H, 2 * sum(map(len, prompts)) * H * D * 2
+    return 4 * D * pairs * H, 2 * sum(map(len, prompts)) * H * D * (1 if FP8 else 2)
 
 
 rng = np.random.default_rng(0)
@@ -59,7 +66,7 @@ for n in ((args.n,) if args.trace else (1, 8, 32, 64)):
         dec = make(n, PATHS[args.trace])
         for _ in range(4):
             call(dec, n, prompts)
-        print(f"trace {args.trace}: n={n} tokens={tok} layers={dims.n_layer}; per attention launch {flops/1e9:.3f} GFLOP, "
+        print(f"trace {args.trace} -> {dec.prefill_attention} (kv_cache_dtype={args.kv_cache_dtype}): n={n} tokens={tok} layers={dims.n_layer}; per attention launch {flops/1e9:.3f} GFLOP, "
               f"unique K/V {kv_bytes/1e6:.2f} MB", flush=True)
         continue
     decs = {name: make(n, kw) for name, kw in PATHS.items()}
@@ -72,14 +79,14 @@ for n in ((args.n,) if args.trace else (1, 8, 32, 64)):
             logits[name] = lg.float().cpu()
     med = {name: float(np.median(v)) for name, v in ts.items()}
     spread = {name: (float(np.min(v)), float(np.max(v))) for name, v in ts.items()}
-    d = {name: (logits[name] - logits["eager"]).abs().max().item() for name in ("positions", "tiled")}
-    same = (logits["tiled"].argmax(-1) == logits["positions"].argmax(-1)).float().mean().item()
-    records.append({"n": n, "tokens": tok, "median_ms": {k: v * 1e3 for k, v in med.items()},
+    d = {name: (logits[name] - logits["eager"]).abs().max().item() for name in ("positions", TILED)}
+    same = (logits[TILED].argmax(-1) == logits["positions"].argmax(-1)).float().mean().item()
+    records.append({"n": n, "tokens": tok, "kv_cache_dtype": args.kv_cache_dtype, "median_ms": {k: v * 1e3 for k, v in med.items()},
                     "min_max_ms": {k: [a * 1e3, b * 1e3] for k, (a, b) in spread.items()},
-                    "max_dlogit_vs_eager": d, "argmax_agree_tiled_positions": same,
+                    "max_dlogit_vs_eager": d, f"argmax_agree_{TILED}_positions": same,
                     "attention_gflop_per_layer": flops / 1e9, "unique_kv_mb_per_layer": kv_bytes / 1e6})
     print(f"n={n:3d} tokens={tok:6d}  " + "  ".join(f"{k} {med[k]*1e3:8.2f} ms ({tok/med[k]/1e3:7.1f} k tok/s)" for k in med) +
-          f"  max|dlogit| vs eager: positions {d['positions']:.3e} tiled {d['tiled']:.3e}  argmax tiled==positions {same:.3f}", flush=True)
+          f"  max|dlogit| vs eager: positions {d['positions']:.3e} {TILED} {d[TILED]:.3e}  argmax {TILED}==positions {same:.3f}", flush=True)
     del decs
     torch.cuda.empty_cache()
 if args.out and records:

@@ -29,6 +29,14 @@ _PA_ARGS = [
     _i64, _i64, _i64,                                # q_stride, kv_block_stride, kv_head_stride
     _i32, _c_void_p,                                 # device, stream
 ]
+_PREFILL_ARGS = [
+    _c_void_p, _c_void_p, _c_void_p, _c_void_p,      # out, query, key_cache, value_cache
+    _i32, _i32, _i32, _i32, _f32,                    # num_tokens, num_heads, head_size, num_kv_heads, scale
+    _c_void_p, _c_void_p, _c_void_p,                 # block_tables, seq_lens, cu_q_lens
+    _i32, _i32, _i32, _i32,                          # num_seqs, max_q_len, block_size, max_num_blocks_per_seq
+    _i64, _i64, _i64,                                # q_stride, kv_block_stride, kv_head_stride
+    _i32, _c_void_p,                                 # device, stream
+]
 
 SIGNATURES = {
     "vmi_abi_version": (ctypes.c_int, []),
@@ -60,14 +68,8 @@ SIGNATURES = {
     "vmi_paged_attention_v2_f16": (ctypes.c_int, [_c_void_p, _c_void_p, _c_void_p] + list(_PA_ARGS) + [_i32]),
     "vmi_paged_attention_v2_variant_count": (ctypes.c_int, []),
     "vmi_paged_attention_v2_variant_name": (ctypes.c_char_p, [_i32]),
-    "vmi_paged_attention_prefill_f16": (ctypes.c_int, [
-        _c_void_p, _c_void_p, _c_void_p, _c_void_p,  # out, query, key_cache, value_cache
-        _i32, _i32, _i32, _i32, _f32,                # num_tokens, num_heads, head_size, num_kv_heads, scale
-        _c_void_p, _c_void_p, _c_void_p,             # block_tables, seq_lens, cu_q_lens
-        _i32, _i32, _i32, _i32,                      # num_seqs, max_q_len, block_size, max_num_blocks_per_seq
-        _i64, _i64, _i64,                            # q_stride, kv_block_stride, kv_head_stride
-        _i32, _c_void_p,                             # device, stream
-    ]),
+    "vmi_paged_attention_prefill_f16": (ctypes.c_int, list(_PREFILL_ARGS)),
+    "vmi_paged_attention_prefill_fp8": (ctypes.c_int, list(_PREFILL_ARGS) + [_f32]),     # ... kv_scale
     "vmi_copy_blocks": (ctypes.c_int, [_c_void_p, _c_void_p, _i32, _c_void_p, _i32, _i64, _i32, _c_void_p]),
     "vmi_swap_blocks": (ctypes.c_int, [_c_void_p, _c_void_p, _c_void_p, _i32, _i64, _i32, _i32, _c_void_p]),
     "vmi_swap_blocks_batched": (ctypes.c_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i32, _i64, _i32, _c_void_p]),

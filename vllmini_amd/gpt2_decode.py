@@ -162,10 +162,17 @@ class GPT2PagedDecoder:
         # matrix cores, every K / V block of a prompt read once per 64 rows instead of once per position, per-SEQUENCE tables
         # (no [layers, sum T, blocks] gather).  Opt-in: the two round differently (fp16 probabilities into an fp32 MFMA sum
         # against the decode kernel's fp16 products).
-        if prefill_attention not in ("positions", "tiled"):
-            raise ValueError(f"prefill_attention must be 'positions' or 'tiled', got {prefill_attention!r}")
-        if prefill_attention == "tiled" and (pool.kv_cache_dtype != "auto" or wdt != torch.float16 or pool.block_size != 16 or
-                                             dims.head_size not in (64, 128)):
+        # "auto" = "tiled" wherever a tiled kernel serves the pool — float16 weights, block size 16, head size 64 / 128, pages
+        # float16 (pa_prefill.hpp) or fp8-E4M3 (pa_prefill_fp8.hpp) — else "positions"; it never raises, and the attribute holds
+        # what it resolved to.
+        if prefill_attention not in ("positions", "tiled", "auto"):
+            raise ValueError(f"prefill_attention must be 'positions', 'tiled' or 'auto', got {prefill_attention!r}")
+        if prefill_attention == "auto":
+            served = wdt == torch.float16 and pool.block_size == 16 and dims.head_size in (64, 128) and \
+                pool.kv_cache_dtype in ("auto", "fp8", "fp8_e4m3")
+            prefill_attention = "tiled" if served else "positions"
+        elif prefill_attention == "tiled" and (pool.kv_cache_dtype != "auto" or wdt != torch.float16 or pool.block_size != 16 or
+                                               dims.head_size not in (64, 128)):
             raise ValueError("prefill_attention='tiled' is built for float16 weights and pages, head size 64 / 128 and block size 16; "
                              f"got {wdt}, kv_cache_dtype='{pool.kv_cache_dtype}', head size {dims.head_size}, block size {pool.block_size}")
         self.prefill_attention = prefill_attention
@@ -289,7 +296,7 @@ class GPT2PagedDecoder:
             a = torch.empty((x.shape[0], E), dtype=x.dtype, device=dev)
             if tiled:
                 ops.paged_attention_prefill(a.view(-1, H, D), q, pool.key_cache, pool.value_cache, H, self.scale, tables_seq[i],
-                                            lens_seq, cu_q, max(lens), pool.block_size)
+                                            lens_seq, cu_q, max(lens), pool.block_size, pool.kv_cache_dtype, pool.kv_scale)
             if paged:
                 ops.paged_attention_v1(a.view(-1, H, D), q, pool.key_cache, pool.value_cache, H, self.scale, tables_tok[i], lens_tok,
                                        pool.block_size, mbe * pool.block_size, None, pool.kv_cache_dtype, pool.kv_scale, 0, 0, 1, 1, 0,

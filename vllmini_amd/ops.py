@@ -483,6 +483,8 @@ def paged_attention_prefill(
     cu_q_lens: torch.Tensor,
     max_q_len: int,
     block_size: int,
+    kv_cache_dtype: str = "auto",
+    kv_scale: float = 1.0,
 ) -> None:
     """Tiled causal attention of a chunk of query rows per sequence over the paged cache (extension: the reference runs its
     prefill as eager masked attention, gpt2.py:46-58); writes `out` in place, returns None.
@@ -491,7 +493,14 @@ def paged_attention_prefill(
     sequence s owns rows cu_q_lens[s] .. cu_q_lens[s+1]-1, which sit at positions seq_lens[s] - q_len .. seq_lens[s] - 1 of the
     blocks in block_tables[s] — their K / V rows are in the cache already (reshape_and_cache first).  seq_lens[s] == q_len is
     a plain prefill, > q_len a chunk over a cached context.  `max_q_len` bounds the q_len of every sequence (host-known: it
-    sizes the grid).  float16 pages, head size 64 / 128, block size 16 (include/vmi_paged_attention.h)."""
+    sizes the grid).  Head size 64 / 128, block size 16; pages float16 (kv_cache_dtype "auto", x = 8) or fp8-E4M3 bytes
+    ("fp8" / "fp8_e4m3", x = 16, uint8 or float8_e4m3fn tensors whose elements mean fp8 * kv_scale — what reshape_and_cache
+    writes); "fp8_e5m2" pages have no prefill kernel (include/vmi_paged_attention.h)."""
+    fp8 = _check_kv_cache_dtype(kv_cache_dtype)     # first: an unknown or unbuilt dtype is reported whatever the tensors are
+    if fp8 == 2:
+        raise RuntimeError(f"paged_attention_prefill is not built for E5M2 pages (kv_cache_dtype='{kv_cache_dtype}'); "
+                           "float16 ('auto') and fp8-E4M3 ('fp8', 'fp8_e4m3') pages are")
+    x = 16 if fp8 else 8
     qs = query.shape
     if len(qs) != 3:
         raise RuntimeError(f"query must be [num_tokens, num_heads, head_size], got {tuple(qs)}")
@@ -507,8 +516,10 @@ def paged_attention_prefill(
     _on("block_tables", block_tables, index, dev)
     _on("seq_lens", seq_lens, index, dev)
     _on("cu_q_lens", cu_q_lens, index, dev)
-    if key_cache.dtype != torch.float16 or value_cache.dtype != torch.float16:
-        raise RuntimeError("key_cache/value_cache must be torch.float16 (paged_attention_prefill is built for kv_cache_dtype='auto')")
+    if fp8:
+        _check_fp8_cache_dtype(fp8, key_cache, value_cache, kv_cache_dtype)
+    elif key_cache.dtype != torch.float16 or value_cache.dtype != torch.float16:
+        raise RuntimeError("key_cache/value_cache must be torch.float16 for kv_cache_dtype='auto' (fp8-E4M3 pages: kv_cache_dtype='fp8')")
     if out.dtype != torch.float16:
         raise RuntimeError(f"out must be torch.float16, got {out.dtype}")
     if block_tables.dtype != torch.int32 or seq_lens.dtype != torch.int32 or cu_q_lens.dtype != torch.int32:
@@ -518,12 +529,12 @@ def paged_attention_prefill(
     if len(ks) != 5 or len(vs) != 4:
         raise RuntimeError("key_cache must be [num_blocks, num_kv_heads, head_size/x, block_size, x] "
                            "and value_cache [num_blocks, num_kv_heads, head_size, block_size]")
-    if ks[4] != 8:
-        raise RuntimeError(f"key_cache innermost dimension must be 8 (16 bytes per chunk), got {ks[4]}")
+    if ks[4] != x:
+        raise RuntimeError(f"key_cache innermost dimension must be {x} (16 bytes per chunk), got {ks[4]}")
     block_size = int(block_size)
     if ks[3] != block_size or vs[3] != block_size:
         raise RuntimeError(f"block_size={block_size} does not match the cache tensors ({ks[3]}, {vs[3]})")
-    if ks[2] * 8 != head_size or vs[2] != head_size:
+    if ks[2] * x != head_size or vs[2] != head_size:
         raise RuntimeError("cache head_size does not match query head_size")
     num_kv_heads = int(num_kv_heads)
     if ks[1] != num_kv_heads or vs[1] != num_kv_heads:
@@ -533,7 +544,7 @@ def paged_attention_prefill(
         raise RuntimeError("query must be contiguous in its last two dimensions")
     kst, vst = key_cache.stride(), value_cache.stride()
     tile = head_size * block_size
-    if kst[4] != 1 or kst[3] != 8 or kst[2] != block_size * 8 or (kst[1] != tile and ks[1] != 1) or vst[3] != 1 or \
+    if kst[4] != 1 or kst[3] != x or kst[2] != block_size * x or (kst[1] != tile and ks[1] != 1) or vst[3] != 1 or \
             vst[2] != block_size or (vst[1] != tile and vs[1] != 1):
         raise RuntimeError("each cache block must be dense")
     if vst[0] != kst[0] or vst[1] != kst[1]:
@@ -548,11 +559,14 @@ def paged_attention_prefill(
         raise RuntimeError("block_tables must be a row-contiguous [num_seqs, max_num_blocks_per_seq] tensor")
     if cu_q_lens.dim() != 1 or cu_q_lens.shape[0] != num_seqs + 1 or not cu_q_lens.is_contiguous():
         raise RuntimeError("cu_q_lens must be a contiguous [num_seqs + 1] tensor")
-    rc = _lib.load().vmi_paged_attention_prefill_f16(
-        out.data_ptr(), query.data_ptr(), key_cache.data_ptr(), value_cache.data_ptr(),
-        num_tokens, num_heads, head_size, num_kv_heads, float(scale),
-        block_tables.data_ptr(), seq_lens.data_ptr(), cu_q_lens.data_ptr(),
-        num_seqs, int(max_q_len), block_size, ts[1], qst[0], kst[0], kst[1], index, _stream_of(index))
+    args = (out.data_ptr(), query.data_ptr(), key_cache.data_ptr(), value_cache.data_ptr(),
+            num_tokens, num_heads, head_size, num_kv_heads, float(scale),
+            block_tables.data_ptr(), seq_lens.data_ptr(), cu_q_lens.data_ptr(),
+            num_seqs, int(max_q_len), block_size, ts[1], qst[0], kst[0], kst[1], index, _stream_of(index))
+    if fp8:
+        rc = _lib.load().vmi_paged_attention_prefill_fp8(*args, float(kv_scale))
+    else:
+        rc = _lib.load().vmi_paged_attention_prefill_f16(*args)
     if rc != 0:
         _raise_native(rc)
     return None
