@@ -430,6 +430,55 @@ int vmi_paged_attention_prefill_fp8(
     int64_t q_stride, int64_t kv_block_stride, int64_t kv_head_stride, int32_t device, void* stream, float kv_scale);
 
 /*
+ * The same operator SPLIT OVER THE CONTEXT (added under ABI 22 like the entries above): for few query rows over a deep
+ * cache — a chunk of a long prompt, verification rows, one long sequence — where one workgroup per 64 rows leaves the chip
+ * idle.  The grid gains a partition axis: a workgroup walks partition_tokens tokens of its rows' causal range and stores
+ * unnormalised fp32 partials (accumulator, running maximum, sum) in `workspace`; a second launch on the same stream merges
+ * a row's partitions 0 .. pos / partition_tokens, in ascending order, and writes `out` (one rounding to fp16).  No atomics, no
+ * waiting between workgroups: results are run-to-run bit-identical.  Kernels: vllmini_amd/csrc/pa_prefill.hpp (SPLIT form),
+ * pa_prefill_fp8.hpp, pa_prefill_split.hpp (merge).
+ *
+ *   max_seq_len       host-known bound on seq_lens, >= 0 and <= 16 * max_num_blocks_per_seq (else VMI_E_SHAPE).  A sequence
+ *                     with seq_lens[s] > max_seq_len writes nothing, like the other malformed lengths.
+ *   partition_tokens  a positive multiple of 32 (else VMI_E_SHAPE); num_partitions = ceil(max_seq_len / partition_tokens).
+ *   workspace         caller-owned device memory, 16-byte aligned, at least the plan's workspace_bytes (else VMI_E_WORKSPACE).
+ *                     Needs no zeroing: every word that is read was written by this call.  Layout: fp32
+ *                     acc[num_partitions][num_tokens][num_heads][head_size], then ml[num_partitions][num_tokens][num_heads][2].
+ *                     Launches that share it must be ordered (one stream).
+ * One partition is valid: the unsplit kernel runs (with the max_seq_len guard) and the workspace is not touched.
+ * Everything else — arguments, validation, masking, accuracy — is vmi_paged_attention_prefill_f16's / _fp8's.
+ */
+int vmi_paged_attention_prefill_split_f16(
+    void* out, const void* query, const void* key_cache, const void* value_cache,
+    int32_t num_tokens, int32_t num_heads, int32_t head_size, int32_t num_kv_heads, float scale,
+    const int32_t* block_tables, const int32_t* seq_lens, const int32_t* cu_q_lens,
+    int32_t num_seqs, int32_t max_q_len, int32_t block_size, int32_t max_num_blocks_per_seq,
+    int64_t q_stride, int64_t kv_block_stride, int64_t kv_head_stride, int32_t device, void* stream,
+    int32_t max_seq_len, int32_t partition_tokens, void* workspace, int64_t workspace_bytes);
+int vmi_paged_attention_prefill_split_fp8(
+    void* out, const void* query, const void* key_cache, const void* value_cache,
+    int32_t num_tokens, int32_t num_heads, int32_t head_size, int32_t num_kv_heads, float scale,
+    const int32_t* block_tables, const int32_t* seq_lens, const int32_t* cu_q_lens,
+    int32_t num_seqs, int32_t max_q_len, int32_t block_size, int32_t max_num_blocks_per_seq,
+    int64_t q_stride, int64_t kv_block_stride, int64_t kv_head_stride, int32_t device, void* stream,
+    int32_t max_seq_len, int32_t partition_tokens, void* workspace, int64_t workspace_bytes, float kv_scale);
+
+/*
+ * Plan of the split launch, pure host arithmetic (no HIP call when num_cus > 0; num_cus == 0 asks the current device).
+ *   partition_tokens_in  > 0: forced (a multiple of 32, else VMI_E_SHAPE); 0: the library's rule — split only when the unsplit
+ *                        grid, ceil(max_q_len / 64) * num_seqs * num_heads workgroups, underfills num_cus AND max_seq_len is
+ *                        deep enough to pay for the merge; then the partition size that brings the grid to a target number of
+ *                        workgroups per CU, not below a floor (constants and their measurements: profiles/prefill_split.md).
+ *   -> partition_tokens, num_partitions = ceil(max_seq_len / partition_tokens) (at least 1),
+ *      workspace_bytes = num_partitions * num_tokens * num_heads * (head_size + 2) * 4, or 0 when num_partitions == 1
+ *      ("do not split").
+ */
+int vmi_paged_attention_prefill_split_plan(
+    int32_t num_tokens, int32_t num_heads, int32_t head_size, int32_t num_seqs, int32_t max_q_len, int32_t max_seq_len,
+    int32_t num_cus, int32_t partition_tokens_in, int32_t* partition_tokens, int32_t* num_partitions,
+    int64_t* workspace_bytes);
+
+/*
  * The pool's preemption move (extension; counterpart of BlockManager.swap_to_cpu / swap_from_cpu,
  * vllmini/block_manager.py:70-87, which the reference runs as one copy per block, cache_kernels.cu:56-62): ONE launch on
  * `stream` moves block_mapping[i] = (src block, dst block) of BOTH caches for every i.

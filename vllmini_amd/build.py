@@ -76,6 +76,7 @@ HDR_QUEUE = os.path.join(CSRC, "pa_queue.hpp")
 HDR_SPLIT = os.path.join(CSRC, "pa_split.hpp")
 HDR_PREFILL = os.path.join(CSRC, "pa_prefill.hpp")
 HDR_PREFILL_FP8 = os.path.join(CSRC, "pa_prefill_fp8.hpp")
+HDR_PREFILL_SPLIT = os.path.join(CSRC, "pa_prefill_split.hpp")
 HDRS_HOST = [os.path.join(CSRC, "pa_host.hpp"), os.path.join(CSRC, "pa_cache_fp8.hpp")]
 INCLUDE = os.path.join(REPO_ROOT, "include")
 OUT_DIR = os.path.join(PKG_DIR, "_C")
@@ -119,7 +120,8 @@ def _units_of(kind: str):
 
 
 def _deps(kind: str = "product") -> list[str]:
-    return [*(s for s, _ in _units_of(kind)), *TABLES, HDR, HDR_QUEUE, HDR_SPLIT, HDR_PREFILL, HDR_PREFILL_FP8, *HDRS_HOST,
+    return [*(s for s, _ in _units_of(kind)), *TABLES, HDR, HDR_QUEUE, HDR_SPLIT, HDR_PREFILL, HDR_PREFILL_FP8, HDR_PREFILL_SPLIT,
+            *HDRS_HOST,
             os.path.join(INCLUDE, "vmi_paged_attention.h"), os.path.join(INCLUDE, "vmi_paged_attention_extras.h"),
             os.path.join(INCLUDE, "vmi_paged_attention_diag.h"),
             os.path.abspath(__file__)]

@@ -5,18 +5,67 @@
 // bounds (num_seqs, max_q_len, num_heads) and surplus workgroups leave at once.
 #include "pa_prefill.hpp"
 #include "pa_prefill_fp8.hpp"
+#include "pa_prefill_split.hpp"
+
+#include <limits.h>
 
 #include "pa_host.hpp"
 #include "vmi_paged_attention.h"
 
 namespace vmi {
 
+// When the launch is split over the context, and how finely (partition_tokens == 0 in the plan).  Every number is read off
+// the tables of profiles/prefill_split.md section 1 (MI355X, 256 CUs); section 2 there walks through them.
+struct SplitRules {
+  int underfill_wgs_per_cu;   // split only when the unsplit grid has FEWER workgroups than this per CU: at 2 per CU (512) the
+                              // split no longer wins consistently, below it wins in every cell measured
+  int min_context;            // ... and max_seq_len is at least this: the shallowest context measured (nothing below it was)
+  int target_wgs_per_cu;      // partitions = what brings the grid to this many workgroups per CU ...
+  int max_partitions;         // ... but no more than this: past 32 the merge's reads outweigh the shorter chains
+  int floor_tokens;           // a partition is never shorter than this: 256 loses to 512 everywhere but the smallest cell
+  int ceil_tokens;            // ... nor longer: 2 048 is the best or within 8 % of the best forced size in every deep cell
+};
+static constexpr SplitRules kSplitRules = {2, 4096, 3, 32, 512, 2048};
+
+// -> VMI_OK and (partition_tokens, num_partitions, workspace_bytes); num_partitions == 1: do not split, 0 bytes
+static int split_plan(int32_t num_tokens, int32_t num_heads, int32_t head_size, int32_t num_seqs, int32_t max_q_len,
+                      int32_t max_seq_len, int32_t num_cus, int32_t partition_tokens_in, int32_t* partition_tokens,
+                      int32_t* num_partitions, int64_t* workspace_bytes) {
+  if (num_tokens < 0 || num_heads <= 0 || num_seqs < 0 || max_q_len < 0 || max_seq_len < 0 || num_cus <= 0)
+    return fail(VMI_E_SHAPE, "paged_attention_prefill_split_plan: negative size (num_tokens=%d num_heads=%d num_seqs=%d "
+                "max_q_len=%d max_seq_len=%d num_cus=%d)", num_tokens, num_heads, num_seqs, max_q_len, max_seq_len, num_cus);
+  if (head_size != 64 && head_size != 128)
+    return fail(VMI_E_HEAD_SIZE, "Unsupported head size: %d (paged_attention_prefill is built for 64 and 128)", head_size);
+  if (partition_tokens_in < 0 || (partition_tokens_in & 31))
+    return fail(VMI_E_SHAPE, "paged_attention_prefill: partition_tokens must be a positive multiple of 32, got %d",
+                partition_tokens_in);
+  int64_t pt = partition_tokens_in;
+  if (pt == 0) {
+    const SplitRules& r = kSplitRules;
+    const int64_t wgs = (((int64_t)max_q_len + prefill::ROWS - 1) / prefill::ROWS) * num_seqs * num_heads;
+    pt = max_seq_len > 32 ? ((int64_t)max_seq_len + 31) & ~31ll : 32;   // one partition
+    if (wgs > 0 && wgs < (int64_t)r.underfill_wgs_per_cu * num_cus && max_seq_len >= r.min_context) {
+      int64_t parts = ((int64_t)r.target_wgs_per_cu * num_cus + wgs - 1) / wgs;
+      if (parts > r.max_partitions) parts = r.max_partitions;
+      pt = ((max_seq_len + parts - 1) / parts + 31) & ~31ll;
+      pt = pt < r.floor_tokens ? r.floor_tokens : pt > r.ceil_tokens ? r.ceil_tokens : pt;
+    }
+  }
+  const int64_t parts = max_seq_len > 0 ? (max_seq_len + pt - 1) / pt : 1;
+  *partition_tokens = (int32_t)pt;
+  *num_partitions = (int32_t)parts;
+  *workspace_bytes = parts > 1 ? parts * num_tokens * num_heads * (head_size + 2) * 4 : 0;
+  return VMI_OK;
+}
+
+// max_seq_len < 0: the plain entries — never split, no bound on seq_lens
 static int launch_pa_prefill(void* out, const void* query, const void* key_cache, const void* value_cache,
                              int32_t num_tokens, int32_t num_heads, int32_t head_size, int32_t num_kv_heads, float scale,
                              const int32_t* block_tables, const int32_t* seq_lens, const int32_t* cu_q_lens,
                              int32_t num_seqs, int32_t max_q_len, int32_t block_size, int32_t max_num_blocks_per_seq,
                              int64_t q_stride, int64_t kv_block_stride, int64_t kv_head_stride, int32_t device,
-                             void* stream, bool fp8, float kv_scale) {
+                             void* stream, bool fp8, float kv_scale, int32_t max_seq_len = -1,
+                             int32_t partition_tokens = 0, void* workspace = nullptr, int64_t workspace_bytes = 0) {
   // one validation for both page formats; the cache strides are in cache elements: halves, or bytes when fp8
   const bool empty = num_tokens == 0 || num_seqs == 0;   // (torch hands out null data pointers for empty tensors)
   if (!key_cache || !value_cache || (!empty && (!out || !query || !block_tables || !seq_lens || !cu_q_lens)))
@@ -39,10 +88,29 @@ static int launch_pa_prefill(void* out, const void* query, const void* key_cache
     return fail(VMI_E_ALIGNMENT, "paged_attention_prefill: query/key_cache/value_cache and their strides must be 16-byte "
                 "aligned (q_stride=%lld kv_block_stride=%lld kv_head_stride=%lld)", (long long)q_stride,
                 (long long)kv_block_stride, (long long)kv_head_stride);
-  if (empty || max_q_len == 0) return VMI_OK;
+  const bool bounded = max_seq_len >= 0;                  // the split entries
+  int32_t parts = 1;
+  if (bounded) {
+    if (max_seq_len > (int64_t)prefill::BS * max_num_blocks_per_seq)
+      return fail(VMI_E_SHAPE, "paged_attention_prefill: max_seq_len=%d exceeds the block table (%d blocks of 16)", max_seq_len,
+                  max_num_blocks_per_seq);
+    if (partition_tokens <= 0 || (partition_tokens & 31))
+      return fail(VMI_E_SHAPE, "paged_attention_prefill: partition_tokens must be a positive multiple of 32, got %d",
+                  partition_tokens);
+    int64_t need = 0;
+    const int rc = split_plan(num_tokens, num_heads, head_size, num_seqs, max_q_len, max_seq_len, 1, partition_tokens,
+                              &partition_tokens, &parts, &need);
+    if (rc != VMI_OK) return rc;
+    if (parts > 1 && !empty && (!workspace || !aligned16(workspace) || workspace_bytes < need))
+      return fail(VMI_E_WORKSPACE, "paged_attention_prefill: %d partitions need a 16-byte aligned workspace of %lld bytes (got %p, %lld bytes)",
+                  parts, (long long)need, workspace, (long long)workspace_bytes);
+  }
+  if (empty || max_q_len == 0 || max_seq_len == 0) return VMI_OK;
   const int64_t groups = ((int64_t)max_q_len + prefill::ROWS - 1) / prefill::ROWS;
-  const int64_t wgs = groups * num_seqs * num_heads;
-  if ((int64_t)num_seqs * num_heads >= (1ll << 31) || wgs >= (1ll << 31))
+  const int64_t wgs = groups * num_seqs * num_heads * parts;
+  constexpr int MERGE_ROWS = 1024 / 128;                  // the merge's rows per workgroup at its smallest (D 128)
+  if ((int64_t)num_seqs * num_heads >= (1ll << 31) || wgs >= (1ll << 31) ||
+      (parts > 1 && ((int64_t)max_q_len + MERGE_ROWS - 1) / MERGE_ROWS * num_seqs * num_heads >= (1ll << 31)))
     return fail(VMI_E_SHAPE, "paged_attention_prefill: %lld workgroups exceed the grid", (long long)wgs);
 
   auto fill = [&](auto& p) {
@@ -61,11 +129,62 @@ static int launch_pa_prefill(void* out, const void* query, const void* key_cache
     p.q_per_kv = num_heads / num_kv_heads;
     p.num_seqs = num_seqs;
     p.max_blocks_per_seq = max_num_blocks_per_seq;
+    p.max_seq_len = bounded ? max_seq_len : INT_MAX;
+    p.ws = static_cast<float*>(workspace);
+    p.part_tokens = partition_tokens;
+    p.num_parts = parts;
+    p.groups = (int32_t)groups;
   };
 
   DeviceGuard guard(device);
   if (guard.err != hipSuccess) return hip_fail(guard.err, "paged_attention_prefill: hipSetDevice");
   const dim3 grid((unsigned)wgs), block(prefill::WAVES * 64);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (parts > 1) {
+    // partition kernels, then the merge, on the caller's stream: the second launch is the only synchronisation
+    prefill::MergeParams mp;
+    mp.out = static_cast<prefill::h16*>(out);
+    mp.ws = static_cast<const float*>(workspace);
+    mp.seq_lens = seq_lens;
+    mp.cu_q_lens = cu_q_lens;
+    mp.num_tokens = num_tokens;
+    mp.num_heads = num_heads;
+    mp.num_seqs = num_seqs;
+    mp.max_blocks_per_seq = max_num_blocks_per_seq;
+    mp.max_seq_len = max_seq_len;
+    mp.part_tokens = partition_tokens;
+    mp.num_parts = parts;
+    mp.out_scale = fp8 ? kv_scale : 1.0f;
+    if (fp8) {
+      prefill::ParamsFp8 p;
+      fill(p);
+      p.scale_log2e = (scale * kv_scale) * 1.4426950408889634f;
+      p.kv_scale = kv_scale;
+      if (head_size == 64)
+        hipLaunchKernelGGL((prefill::pa_prefill_fp8_kernel<64, true>), grid, block, 0, st, p);
+      else
+        hipLaunchKernelGGL((prefill::pa_prefill_fp8_kernel<128, true>), grid, block, 0, st, p);
+    } else {
+      prefill::Params p;
+      fill(p);
+      p.scale_log2e = scale * 1.4426950408889634f;
+      if (head_size == 64)
+        hipLaunchKernelGGL((prefill::pa_prefill_kernel<64, true>), grid, block, 0, st, p);
+      else
+        hipLaunchKernelGGL((prefill::pa_prefill_kernel<128, true>), grid, block, 0, st, p);
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "paged_attention_prefill partition launch");
+    const int rpb = 1024 / head_size;
+    const dim3 mgrid((unsigned)(((int64_t)max_q_len + rpb - 1) / rpb * num_seqs * num_heads));
+    if (head_size == 64)
+      hipLaunchKernelGGL(prefill::pa_prefill_merge_kernel<64>, mgrid, dim3(256), 0, st, mp);
+    else
+      hipLaunchKernelGGL(prefill::pa_prefill_merge_kernel<128>, mgrid, dim3(256), 0, st, mp);
+    e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "paged_attention_prefill merge launch");
+    return VMI_OK;
+  }
   if (fp8) {
     prefill::ParamsFp8 p;
     fill(p);
@@ -111,4 +230,50 @@ extern "C" int vmi_paged_attention_prefill_fp8(
   return vmi::launch_pa_prefill(out, query, key_cache, value_cache, num_tokens, num_heads, head_size, num_kv_heads, scale,
                                 block_tables, seq_lens, cu_q_lens, num_seqs, max_q_len, block_size, max_num_blocks_per_seq,
                                 q_stride, kv_block_stride, kv_head_stride, device, stream, true, kv_scale);
+}
+
+extern "C" int vmi_paged_attention_prefill_split_plan(
+    int32_t num_tokens, int32_t num_heads, int32_t head_size, int32_t num_seqs, int32_t max_q_len, int32_t max_seq_len,
+    int32_t num_cus, int32_t partition_tokens_in, int32_t* partition_tokens, int32_t* num_partitions,
+    int64_t* workspace_bytes) {
+  if (!partition_tokens || !num_partitions || !workspace_bytes)
+    return vmi::fail(VMI_E_NULL_POINTER, "paged_attention_prefill_split_plan: NULL result pointer");
+  if (num_cus == 0) {   // ask the current device
+    int dev = 0;
+    hipDeviceProp_t prop;
+    hipError_t e = hipGetDevice(&dev);
+    if (e == hipSuccess) e = hipGetDeviceProperties(&prop, dev);
+    if (e != hipSuccess) return vmi::hip_fail(e, "paged_attention_prefill_split_plan: device properties");
+    num_cus = prop.multiProcessorCount;
+  }
+  return vmi::split_plan(num_tokens, num_heads, head_size, num_seqs, max_q_len, max_seq_len, num_cus, partition_tokens_in,
+                         partition_tokens, num_partitions, workspace_bytes);
+}
+
+extern "C" int vmi_paged_attention_prefill_split_f16(
+    void* out, const void* query, const void* key_cache, const void* value_cache,
+    int32_t num_tokens, int32_t num_heads, int32_t head_size, int32_t num_kv_heads, float scale,
+    const int32_t* block_tables, const int32_t* seq_lens, const int32_t* cu_q_lens,
+    int32_t num_seqs, int32_t max_q_len, int32_t block_size, int32_t max_num_blocks_per_seq,
+    int64_t q_stride, int64_t kv_block_stride, int64_t kv_head_stride, int32_t device, void* stream,
+    int32_t max_seq_len, int32_t partition_tokens, void* workspace, int64_t workspace_bytes) {
+  if (max_seq_len < 0) return vmi::fail(VMI_E_SHAPE, "paged_attention_prefill: negative max_seq_len=%d", max_seq_len);
+  return vmi::launch_pa_prefill(out, query, key_cache, value_cache, num_tokens, num_heads, head_size, num_kv_heads, scale,
+                                block_tables, seq_lens, cu_q_lens, num_seqs, max_q_len, block_size, max_num_blocks_per_seq,
+                                q_stride, kv_block_stride, kv_head_stride, device, stream, false, 1.0f, max_seq_len,
+                                partition_tokens, workspace, workspace_bytes);
+}
+
+extern "C" int vmi_paged_attention_prefill_split_fp8(
+    void* out, const void* query, const void* key_cache, const void* value_cache,
+    int32_t num_tokens, int32_t num_heads, int32_t head_size, int32_t num_kv_heads, float scale,
+    const int32_t* block_tables, const int32_t* seq_lens, const int32_t* cu_q_lens,
+    int32_t num_seqs, int32_t max_q_len, int32_t block_size, int32_t max_num_blocks_per_seq,
+    int64_t q_stride, int64_t kv_block_stride, int64_t kv_head_stride, int32_t device, void* stream,
+    int32_t max_seq_len, int32_t partition_tokens, void* workspace, int64_t workspace_bytes, float kv_scale) {
+  if (max_seq_len < 0) return vmi::fail(VMI_E_SHAPE, "paged_attention_prefill: negative max_seq_len=%d", max_seq_len);
+  return vmi::launch_pa_prefill(out, query, key_cache, value_cache, num_tokens, num_heads, head_size, num_kv_heads, scale,
+                                block_tables, seq_lens, cu_q_lens, num_seqs, max_q_len, block_size, max_num_blocks_per_seq,
+                                q_stride, kv_block_stride, kv_head_stride, device, stream, true, kv_scale, max_seq_len,
+                                partition_tokens, workspace, workspace_bytes);
 }

@@ -61,27 +61,67 @@ struct Params {
   int64_t q_stride, kv_block_stride, kv_head_stride;
   int32_t num_tokens, num_heads, q_per_kv, num_seqs, max_blocks_per_seq;
   float scale_log2e;            // scale * log2(e): the softmax runs on exp2
+  int32_t max_seq_len;          // host-known bound on seq_lens: a longer sequence writes nothing (INT32_MAX: no bound)
+  // the partition form only (SPLIT, see below)
+  float* ws;                    // partials: [parts][num_tokens][num_heads][D] fp32, then [parts][num_tokens][num_heads][2]
+  int32_t part_tokens, num_parts, groups;   // tokens per context partition (a multiple of 32), partitions, the host's bound on 64-row groups
 };
+
+// THE guard of every kernel of the operator (unsplit, partition form, merge): a sequence with nothing to do, or with
+// lengths the tensors cannot hold or the host did not plan for, writes nothing.  -> false: leave.
+template <class P>
+__device__ __forceinline__ bool seq_span(const P& p, int seq, int& row_lo, int& q_len, int& L) {
+  row_lo = p.cu_q_lens[seq];
+  const int row_hi = p.cu_q_lens[seq + 1];
+  q_len = row_hi - row_lo;
+  L = p.seq_lens[seq];
+  return !(q_len <= 0 || L <= 0 || L - q_len < 0 || row_lo < 0 || row_hi > p.num_tokens ||
+           (L + BS - 1) / BS > p.max_blocks_per_seq || L > p.max_seq_len);
+}
+
+// The partition form's epilogue: lane (n, kg) stores its column's UNNORMALISED fp32 accumulator — dims 16t + 4kg .. + 3 of
+// row `row`, in the natural dim order: four lanes fill 64 contiguous bytes per t — and lane kg == 0 the column's running
+// maximum (log2 domain) and sum.  Layout: acc[part][row][head][D], then ml[part][row][head][2].
+template <int D>
+__device__ __forceinline__ void store_partial(float* ws, int num_tokens, int num_heads, int num_parts, int part, int row,
+                                              int head, int kg, const f32x4 (&o)[D / 16], float m, float lsum) {
+  const int64_t item = ((int64_t)part * num_tokens + row) * num_heads + head;
+  float* ap = ws + item * D + 4 * kg;
+#pragma unroll
+  for (int t = 0; t < D / 16; ++t) *reinterpret_cast<f32x4*>(ap + 16 * t) = o[t];
+  if (kg == 0) {
+    typedef float f32x2 __attribute__((ext_vector_type(2)));
+    *reinterpret_cast<f32x2*>(ws + (int64_t)num_parts * num_tokens * num_heads * D + item * 2) = f32x2{m, lsum};
+  }
+}
 
 // Grid: one workgroup per (64-row group, sequence, head), x = group_rev * (num_seqs * num_heads) + seq * num_heads + head.
 // group_rev counts a sequence's groups from its LAST one, so the first num_seqs * num_heads workgroups of the launch are
 // every sequence's longest causal range; a sequence with fewer groups than the host bound leaves the surplus at once.
-template <int D>
+//
+// SPLIT (the partition form, for few rows over a deep context): the grid gains a partition axis, x = (part * groups +
+// group_rev) * (num_seqs * num_heads) + seq * num_heads + head, and a tile walks only the pairs of its partition
+// [part * part_tokens, min((part + 1) * part_tokens, last_pos + 1)) — the trip itself is the same code.  It does not
+// normalise and writes nothing to `out`: store_partial(), merged by pa_prefill_merge_kernel (pa_prefill_split.hpp) in a
+// second launch.  Partition is the OUTER index, ascending: every chain is at most part_tokens / 32 trips, the full ones are
+// all alike, and the lower a partition the more tiles own all of it — so the launch starts with the workgroups that all
+// work their full length, and those that leave at once (partitions past a sequence's end) come last.  Neighbours in x are
+// the heads of one sequence in one partition: the query heads of a KV head read the same pages at the same time.
+template <int D, bool SPLIT = false>
 __global__ void __launch_bounds__(WAVES * 64) pa_prefill_kernel(const Params p) {
   constexpr int KC = D / 32;    // 32-dim chunks of a K block: one MFMA each
   constexpr int VT = D / 16;    // 16-dim tiles of the output: one MFMA each
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int items = p.num_seqs * p.num_heads;
-  const int grev = blockIdx.x / items;
-  const int rem = blockIdx.x - grev * items;
+  const int slot = blockIdx.x / items;
+  const int rem = blockIdx.x - slot * items;
   const int seq = rem / p.num_heads, head = rem - seq * p.num_heads;
-  const int row_lo = p.cu_q_lens[seq], row_hi = p.cu_q_lens[seq + 1];
-  const int q_len = row_hi - row_lo, L = p.seq_lens[seq];
+  const int part = SPLIT ? slot / p.groups : 0;      // my context partition: tokens part * part_tokens .. + part_tokens - 1
+  const int grev = SPLIT ? slot - part * p.groups : slot;
+  int row_lo, q_len, L;
+  if (!seq_span(p, seq, row_lo, q_len, L)) return;
   const int ctx = L - q_len;    // cached positions in front of the chunk
-  // nothing to do, or lengths the tensors cannot hold: the sequence writes nothing
-  if (q_len <= 0 || L <= 0 || ctx < 0 || row_lo < 0 || row_hi > p.num_tokens || (L + BS - 1) / BS > p.max_blocks_per_seq)
-    return;
   const int ngroups = (q_len + ROWS - 1) / ROWS;
   if (grev >= ngroups) return;
   const int j0 = ((ngroups - 1 - grev) * WAVES + wave) * TILE;   // first row of my tile within the chunk
@@ -92,6 +132,13 @@ __global__ void __launch_bounds__(WAVES * 64) pa_prefill_kernel(const Params p) 
   const int pos = ctx + jr;                              // my column's position: it attends to tokens 0..pos
   const int last_pos = ctx + min(j0 + TILE - 1, q_len - 1);
   const int nblk = last_pos / BS + 1, npair = (nblk + 1) >> 1;
+  // the trips I walk: all of them, or my partition's (it starts on a pair boundary; a tile that ends below it leaves)
+  int pp0 = 0, pp1 = npair;
+  if constexpr (SPLIT) {
+    if (last_pos < part * p.part_tokens) return;           // (wave-uniform)
+    pp0 = part * (p.part_tokens >> 5);
+    pp1 = min(npair, pp0 + (p.part_tokens >> 5));
+  }
 
   const h16* qp = p.q + (int64_t)(row_lo + jr) * p.q_stride + (int64_t)head * D + 8 * kg;
   h16x8 qB[KC];
@@ -132,10 +179,10 @@ __global__ void __launch_bounds__(WAVES * 64) pa_prefill_kernel(const Params p) 
 
   h16x8 kcur[2][KC], knext[2][KC];
   u32x2 v[2][VT];
-  load_k(kcur, 0);
-  for (int pp = 0; pp < npair; ++pp) {
+  load_k(kcur, pp0);
+  for (int pp = pp0; pp < pp1; ++pp) {
     load_v(v, pp);
-    load_k(knext, min(pp + 1, npair - 1));   // (the last trip re-reads its own pair: no branch around the loads)
+    load_k(knext, min(pp + 1, pp1 - 1));   // (the last trip re-reads its own pair: no branch around the loads)
 
     // ---- S^T = K . Q^T, scaled in fp32, causal mask selected ----
     float s[2][4];
@@ -196,6 +243,12 @@ __global__ void __launch_bounds__(WAVES * 64) pa_prefill_kernel(const Params p) 
 
   lsum += __shfl_xor(lsum, 16);
   lsum += __shfl_xor(lsum, 32);
+  if constexpr (SPLIT) {
+    // unnormalised partials of the columns that see a token of this partition (the others hold sum 0 and are never merged)
+    if (j0 + n < q_len && pos >= part * p.part_tokens)
+      store_partial<D>(p.ws, p.num_tokens, p.num_heads, p.num_parts, part, row_lo + j0 + n, head, kg, o, m, lsum);
+    return;
+  }
   if (j0 + n < q_len) {
     const float inv = 1.f / lsum;   // (a stored row attends at least to token 0 and its maximum contributes exp2(0): lsum >= 1)
     h16* op = p.out + ((int64_t)(row_lo + j0 + n) * p.num_heads + head) * D + 4 * kg;

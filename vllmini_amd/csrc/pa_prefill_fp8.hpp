@@ -41,6 +41,9 @@ struct ParamsFp8 {
   int32_t num_tokens, num_heads, q_per_kv, num_seqs, max_blocks_per_seq;
   float scale_log2e;            // scale * kv_scale * log2(e)
   float kv_scale;               // V's factor: applied with the final 1 / sum
+  int32_t max_seq_len;          // as Params: the guard's bound, and the partition form's fields
+  float* ws;
+  int32_t part_tokens, num_parts, groups;
 };
 
 // four E4M3 bytes -> four halves (two dwords of half pairs), element order kept
@@ -54,23 +57,23 @@ __device__ __forceinline__ h16x8 e4m3x8_to_h16x8(uint32_t w0, uint32_t w1) {
   return __builtin_bit_cast(h16x8, u32x4{a[0], a[1], b[0], b[1]});
 }
 
-// Grid: as pa_prefill_kernel — x = group_rev * (num_seqs * num_heads) + seq * num_heads + head.
-template <int D>
+// Grid: as pa_prefill_kernel — x = group_rev * (num_seqs * num_heads) + seq * num_heads + head; SPLIT: its partition form
+// (partition outer, store_partial() instead of the normalised store; V partials leave WITHOUT kv_scale: the merge applies it).
+template <int D, bool SPLIT = false>
 __global__ void __launch_bounds__(WAVES * 64) pa_prefill_fp8_kernel(const ParamsFp8 p) {
   constexpr int KG = D / 64;    // 64-dim groups of a K block: one 16-byte load, two MFMAs each
   constexpr int VT = D / 16;    // 16-dim tiles of the output: one dword per block, one MFMA each
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int items = p.num_seqs * p.num_heads;
-  const int grev = blockIdx.x / items;
-  const int rem = blockIdx.x - grev * items;
+  const int slot = blockIdx.x / items;
+  const int rem = blockIdx.x - slot * items;
   const int seq = rem / p.num_heads, head = rem - seq * p.num_heads;
-  const int row_lo = p.cu_q_lens[seq], row_hi = p.cu_q_lens[seq + 1];
-  const int q_len = row_hi - row_lo, L = p.seq_lens[seq];
+  const int part = SPLIT ? slot / p.groups : 0;      // my context partition: tokens part * part_tokens .. + part_tokens - 1
+  const int grev = SPLIT ? slot - part * p.groups : slot;
+  int row_lo, q_len, L;
+  if (!seq_span(p, seq, row_lo, q_len, L)) return;
   const int ctx = L - q_len;    // cached positions in front of the chunk
-  // nothing to do, or lengths the tensors cannot hold: the sequence writes nothing
-  if (q_len <= 0 || L <= 0 || ctx < 0 || row_lo < 0 || row_hi > p.num_tokens || (L + BS - 1) / BS > p.max_blocks_per_seq)
-    return;
   const int ngroups = (q_len + ROWS - 1) / ROWS;
   if (grev >= ngroups) return;
   const int j0 = ((ngroups - 1 - grev) * WAVES + wave) * TILE;   // first row of my tile within the chunk
@@ -81,6 +84,13 @@ __global__ void __launch_bounds__(WAVES * 64) pa_prefill_fp8_kernel(const Params
   const int pos = ctx + jr;                              // my column's position: it attends to tokens 0..pos
   const int last_pos = ctx + min(j0 + TILE - 1, q_len - 1);
   const int nblk = last_pos / BS + 1, npair = (nblk + 1) >> 1;
+  // the trips I walk: all of them, or my partition's (it starts on a pair boundary; a tile that ends below it leaves)
+  int pp0 = 0, pp1 = npair;
+  if constexpr (SPLIT) {
+    if (last_pos < part * p.part_tokens) return;           // (wave-uniform)
+    pp0 = part * (p.part_tokens >> 5);
+    pp1 = min(npair, pp0 + (p.part_tokens >> 5));
+  }
 
   // Q^T in the permuted k order of the K operand: for MFMA (g, j) dims 64g + 16kg + 8j .. +7
   const h16* qp = p.q + (int64_t)(row_lo + jr) * p.q_stride + (int64_t)head * D + 16 * kg;
@@ -124,10 +134,10 @@ __global__ void __launch_bounds__(WAVES * 64) pa_prefill_fp8_kernel(const Params
 
   u32x4 kcur[2][KG], knext[2][KG];
   uint32_t v[2][VT];
-  load_k(kcur, 0);
-  for (int pp = 0; pp < npair; ++pp) {
+  load_k(kcur, pp0);
+  for (int pp = pp0; pp < pp1; ++pp) {
     load_v(v, pp);
-    load_k(knext, min(pp + 1, npair - 1));   // (the last trip re-reads its own pair: no branch around the loads)
+    load_k(knext, min(pp + 1, pp1 - 1));   // (the last trip re-reads its own pair: no branch around the loads)
 
     // ---- S^T = K . Q^T, scaled in fp32 (kv_scale included), causal mask selected ----
     float s[2][4];
@@ -189,6 +199,12 @@ __global__ void __launch_bounds__(WAVES * 64) pa_prefill_fp8_kernel(const Params
 
   lsum += __shfl_xor(lsum, 16);
   lsum += __shfl_xor(lsum, 32);
+  if constexpr (SPLIT) {
+    // unnormalised partials of the columns that see a token of this partition (the others hold sum 0 and are never merged)
+    if (j0 + n < q_len && pos >= part * p.part_tokens)
+      store_partial<D>(p.ws, p.num_tokens, p.num_heads, p.num_parts, part, row_lo + j0 + n, head, kg, o, m, lsum);
+    return;
+  }
   if (j0 + n < q_len) {
     const float inv = p.kv_scale / lsum;   // (a stored row attends at least to token 0: lsum >= 1)
     h16* op = p.out + ((int64_t)(row_lo + j0 + n) * p.num_heads + head) * D + 4 * kg;

@@ -36,6 +36,7 @@ __all__ = [
     "reshape_and_cache",
     "pick_variant",
     "workspace_for",
+    "prefill_workspace_for",
     "reset_workspaces",
     "variant_fits",
     "variant_names",
@@ -471,6 +472,41 @@ def paged_attention_v2(
     return None
 
 
+# ---- the wrapper-owned workspace of the context-split prefill: the partition kernels' fp32 partials.  Per (device, stream)
+# like _WS, grown on demand to the plan's bytes, never zeroed (every word the merge reads was written by the same call) and
+# never allocated during stream capture.
+_PWS: dict = {}
+_NUM_CUS: dict = {}
+
+
+def prefill_workspace_for(index: int, nbytes: int, stream: Optional[int] = None) -> Optional[torch.Tensor]:
+    """The uint8 tensor paged_attention_prefill hands to the split launch on (device `index`, its current stream), at least
+    `nbytes` long — None when it would have to be allocated during stream capture."""
+    if stream is None:
+        stream = _stream_of(index)
+    ws = _PWS.get((index, stream))
+    if ws is None or ws.numel() < nbytes:
+        if _capturing():
+            return None
+        ws = _PWS[(index, stream)] = torch.empty(int(nbytes), dtype=torch.uint8, device=torch.device("cuda", index))
+    return ws
+
+
+def prefill_split_plan(num_tokens: int, num_heads: int, head_size: int, num_seqs: int, max_q_len: int, max_seq_len: int,
+                       num_cus: int = 0, partition_tokens: int = 0) -> tuple:
+    """(partition_tokens, num_partitions, workspace_bytes) of the context-split prefill launch: the library's rule
+    (partition_tokens=0) or a forced partition size.  num_cus=0 asks the current device.  One partition = do not split."""
+    import ctypes
+
+    pt, parts, nbytes = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int64()
+    rc = _lib.load().vmi_paged_attention_prefill_split_plan(int(num_tokens), int(num_heads), int(head_size), int(num_seqs),
+                                                            int(max_q_len), int(max_seq_len), int(num_cus), int(partition_tokens),
+                                                            ctypes.byref(pt), ctypes.byref(parts), ctypes.byref(nbytes))
+    if rc != 0:
+        _raise_native(rc)
+    return pt.value, parts.value, nbytes.value
+
+
 def paged_attention_prefill(
     out: torch.Tensor,
     query: torch.Tensor,
@@ -485,6 +521,8 @@ def paged_attention_prefill(
     block_size: int,
     kv_cache_dtype: str = "auto",
     kv_scale: float = 1.0,
+    max_seq_len: Optional[int] = None,
+    partition_tokens: Optional[int] = None,
 ) -> None:
     """Tiled causal attention of a chunk of query rows per sequence over the paged cache (extension: the reference runs its
     prefill as eager masked attention, gpt2.py:46-58); writes `out` in place, returns None.
@@ -495,7 +533,16 @@ def paged_attention_prefill(
     a plain prefill, > q_len a chunk over a cached context.  `max_q_len` bounds the q_len of every sequence (host-known: it
     sizes the grid).  Head size 64 / 128, block size 16; pages float16 (kv_cache_dtype "auto", x = 8) or fp8-E4M3 bytes
     ("fp8" / "fp8_e4m3", x = 16, uint8 or float8_e4m3fn tensors whose elements mean fp8 * kv_scale — what reshape_and_cache
-    writes); "fp8_e5m2" pages have no prefill kernel (include/vmi_paged_attention.h)."""
+    writes); "fp8_e5m2" pages have no prefill kernel (include/vmi_paged_attention.h).
+
+    `max_seq_len` (a host-known bound on seq_lens; None: today's single launch) lets the launch SPLIT OVER THE CONTEXT: few rows
+    over a deep cache — a chunk of a long prompt, verification rows, one long sequence — are spread over partitions of the
+    context that meet in a wrapper-owned workspace (prefill_workspace_for) and a merge launch.  The library's rule decides
+    from the host-known bounds whether and how finely (prefill_split_plan; profiles/prefill_split.md); `partition_tokens` (a
+    multiple of 32, needs max_seq_len) forces the size, for tests and tuning.  A sequence longer than max_seq_len writes
+    nothing.  Under stream capture with no cached workspace large enough, the single launch is taken."""
+    if max_seq_len is None and partition_tokens is not None:
+        raise RuntimeError("paged_attention_prefill: partition_tokens needs max_seq_len (the host-known bound on seq_lens)")
     fp8 = _check_kv_cache_dtype(kv_cache_dtype)     # first: an unknown or unbuilt dtype is reported whatever the tensors are
     if fp8 == 2:
         raise RuntimeError(f"paged_attention_prefill is not built for E5M2 pages (kv_cache_dtype='{kv_cache_dtype}'); "
@@ -563,10 +610,25 @@ def paged_attention_prefill(
             num_tokens, num_heads, head_size, num_kv_heads, float(scale),
             block_tables.data_ptr(), seq_lens.data_ptr(), cu_q_lens.data_ptr(),
             num_seqs, int(max_q_len), block_size, ts[1], qst[0], kst[0], kst[1], index, _stream_of(index))
-    if fp8:
-        rc = _lib.load().vmi_paged_attention_prefill_fp8(*args, float(kv_scale))
+    lib = _lib.load()
+    if max_seq_len is not None:
+        cus = _NUM_CUS.get(index)
+        if cus is None:
+            cus = _NUM_CUS[index] = int(torch.cuda.get_device_properties(index).multi_processor_count)
+        pt, parts, nbytes = prefill_split_plan(num_tokens, num_heads, head_size, num_seqs, max_q_len, max_seq_len, cus,
+                                               int(partition_tokens or 0))
+        ws = prefill_workspace_for(index, nbytes, args[-1]) if parts > 1 else None
+        if ws is None:                                  # one partition (or capturing without a workspace): the single launch
+            pt, ws_ptr, ws_len = max(32, (int(max_seq_len) + 31) // 32 * 32), None, 0
+        else:
+            ws_ptr, ws_len = ws.data_ptr(), ws.numel()
+        tail = (int(max_seq_len), pt, ws_ptr, ws_len)
+        rc = lib.vmi_paged_attention_prefill_split_fp8(*args, *tail, float(kv_scale)) if fp8 else \
+            lib.vmi_paged_attention_prefill_split_f16(*args, *tail)
+    elif fp8:
+        rc = lib.vmi_paged_attention_prefill_fp8(*args, float(kv_scale))
     else:
-        rc = _lib.load().vmi_paged_attention_prefill_f16(*args)
+        rc = lib.vmi_paged_attention_prefill_f16(*args)
     if rc != 0:
         _raise_native(rc)
     return None
