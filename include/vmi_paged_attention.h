@@ -479,6 +479,33 @@ int vmi_paged_attention_prefill_split_plan(
     int64_t* workspace_bytes);
 
 /*
+ * The same operator in its COOPERATIVE form (added under ABI 22 like the entries above): for 64-row groups with at most 16
+ * live rows — a decode row, look-ahead or verification rows, the tail of a chunk, a 16-row chunk over a deep cache — where
+ * three of a workgroup's four waves have no tile and the fourth walks the whole causal range alone.  In such a group all four
+ * waves take the one tile, wave w the pairs of blocks w, w + 4, ... of the range (of the partition, when split), and meet once
+ * in LDS: maximum first, then the weighted sums in ascending wave order, fp32 — the merge launch's arithmetic, no atomics,
+ * run-to-run bit-identical.  A group with more than 16 live rows computes bit for bit what vmi_paged_attention_prefill_split_*
+ * computes.  Kernels: the COOP form in vllmini_amd/csrc/pa_prefill.hpp / pa_prefill_fp8.hpp.
+ * Arguments and validation are vmi_paged_attention_prefill_split_f16's / _fp8's: one partition (partition_tokens >=
+ * max_seq_len; workspace may be NULL) is one cooperative launch, more partitions the cooperative partition kernels and the
+ * same merge launch over the same workspace layout.
+ */
+int vmi_paged_attention_prefill_coop_f16(
+    void* out, const void* query, const void* key_cache, const void* value_cache,
+    int32_t num_tokens, int32_t num_heads, int32_t head_size, int32_t num_kv_heads, float scale,
+    const int32_t* block_tables, const int32_t* seq_lens, const int32_t* cu_q_lens,
+    int32_t num_seqs, int32_t max_q_len, int32_t block_size, int32_t max_num_blocks_per_seq,
+    int64_t q_stride, int64_t kv_block_stride, int64_t kv_head_stride, int32_t device, void* stream,
+    int32_t max_seq_len, int32_t partition_tokens, void* workspace, int64_t workspace_bytes);
+int vmi_paged_attention_prefill_coop_fp8(
+    void* out, const void* query, const void* key_cache, const void* value_cache,
+    int32_t num_tokens, int32_t num_heads, int32_t head_size, int32_t num_kv_heads, float scale,
+    const int32_t* block_tables, const int32_t* seq_lens, const int32_t* cu_q_lens,
+    int32_t num_seqs, int32_t max_q_len, int32_t block_size, int32_t max_num_blocks_per_seq,
+    int64_t q_stride, int64_t kv_block_stride, int64_t kv_head_stride, int32_t device, void* stream,
+    int32_t max_seq_len, int32_t partition_tokens, void* workspace, int64_t workspace_bytes, float kv_scale);
+
+/*
  * The pool's preemption move (extension; counterpart of BlockManager.swap_to_cpu / swap_from_cpu,
  * vllmini/block_manager.py:70-87, which the reference runs as one copy per block, cache_kernels.cu:56-62): ONE launch on
  * `stream` moves block_mapping[i] = (src block, dst block) of BOTH caches for every i.

@@ -73,6 +73,9 @@ SIGNATURES = {
     # the prefill split over the context: ... max_seq_len, partition_tokens, workspace, workspace_bytes [, kv_scale]
     "vmi_paged_attention_prefill_split_f16": (ctypes.c_int, list(_PREFILL_ARGS) + [_i32, _i32, _c_void_p, _i64]),
     "vmi_paged_attention_prefill_split_fp8": (ctypes.c_int, list(_PREFILL_ARGS) + [_i32, _i32, _c_void_p, _i64, _f32]),
+    # the cooperative form (a short tile shared by the workgroup's four waves): the split entries' arguments
+    "vmi_paged_attention_prefill_coop_f16": (ctypes.c_int, list(_PREFILL_ARGS) + [_i32, _i32, _c_void_p, _i64]),
+    "vmi_paged_attention_prefill_coop_fp8": (ctypes.c_int, list(_PREFILL_ARGS) + [_i32, _i32, _c_void_p, _i64, _f32]),
     # num_tokens, num_heads, head_size, num_seqs, max_q_len, max_seq_len, num_cus, partition_tokens_in, -> 3 results
     "vmi_paged_attention_prefill_split_plan": (ctypes.c_int, [_i32] * 8 + [ctypes.POINTER(_i32), ctypes.POINTER(_i32),
                                                                        ctypes.POINTER(_i64)]),

@@ -58,14 +58,39 @@ static int split_plan(int32_t num_tokens, int32_t num_heads, int32_t head_size, 
   return VMI_OK;
 }
 
-// max_seq_len < 0: the plain entries — never split, no bound on seq_lens
+// The tile kernel of (page format by the Params type, head size, form): one place for the twelve instantiations
+template <bool SPLIT, bool COOP>
+static void launch_tiles(const prefill::Params& p, int head_size, dim3 grid, dim3 block, hipStream_t st) {
+  if (head_size == 64)
+    hipLaunchKernelGGL((prefill::pa_prefill_kernel<64, SPLIT, COOP>), grid, block, 0, st, p);
+  else
+    hipLaunchKernelGGL((prefill::pa_prefill_kernel<128, SPLIT, COOP>), grid, block, 0, st, p);
+}
+template <bool SPLIT, bool COOP>
+static void launch_tiles(const prefill::ParamsFp8& p, int head_size, dim3 grid, dim3 block, hipStream_t st) {
+  if (head_size == 64)
+    hipLaunchKernelGGL((prefill::pa_prefill_fp8_kernel<64, SPLIT, COOP>), grid, block, 0, st, p);
+  else
+    hipLaunchKernelGGL((prefill::pa_prefill_fp8_kernel<128, SPLIT, COOP>), grid, block, 0, st, p);
+}
+template <bool SPLIT, class P>
+static void launch_tiles(const P& p, int head_size, bool coop, dim3 grid, dim3 block, hipStream_t st) {
+  if (coop)
+    launch_tiles<SPLIT, true>(p, head_size, grid, block, st);
+  else
+    launch_tiles<SPLIT, false>(p, head_size, grid, block, st);
+}
+
+// max_seq_len < 0: the plain entries — never split, no bound on seq_lens.  coop: the cooperative form of the tile kernels
+// (pa_prefill.hpp, COOP) — same grid, same Params, same merge launch.
 static int launch_pa_prefill(void* out, const void* query, const void* key_cache, const void* value_cache,
                              int32_t num_tokens, int32_t num_heads, int32_t head_size, int32_t num_kv_heads, float scale,
                              const int32_t* block_tables, const int32_t* seq_lens, const int32_t* cu_q_lens,
                              int32_t num_seqs, int32_t max_q_len, int32_t block_size, int32_t max_num_blocks_per_seq,
                              int64_t q_stride, int64_t kv_block_stride, int64_t kv_head_stride, int32_t device,
                              void* stream, bool fp8, float kv_scale, int32_t max_seq_len = -1,
-                             int32_t partition_tokens = 0, void* workspace = nullptr, int64_t workspace_bytes = 0) {
+                             int32_t partition_tokens = 0, void* workspace = nullptr, int64_t workspace_bytes = 0,
+                             bool coop = false) {
   // one validation for both page formats; the cache strides are in cache elements: halves, or bytes when fp8
   const bool empty = num_tokens == 0 || num_seqs == 0;   // (torch hands out null data pointers for empty tensors)
   if (!key_cache || !value_cache || (!empty && (!out || !query || !block_tables || !seq_lens || !cu_q_lens)))
@@ -160,18 +185,12 @@ static int launch_pa_prefill(void* out, const void* query, const void* key_cache
       fill(p);
       p.scale_log2e = (scale * kv_scale) * 1.4426950408889634f;
       p.kv_scale = kv_scale;
-      if (head_size == 64)
-        hipLaunchKernelGGL((prefill::pa_prefill_fp8_kernel<64, true>), grid, block, 0, st, p);
-      else
-        hipLaunchKernelGGL((prefill::pa_prefill_fp8_kernel<128, true>), grid, block, 0, st, p);
+      launch_tiles<true>(p, head_size, coop, grid, block, st);
     } else {
       prefill::Params p;
       fill(p);
       p.scale_log2e = scale * 1.4426950408889634f;
-      if (head_size == 64)
-        hipLaunchKernelGGL((prefill::pa_prefill_kernel<64, true>), grid, block, 0, st, p);
-      else
-        hipLaunchKernelGGL((prefill::pa_prefill_kernel<128, true>), grid, block, 0, st, p);
+      launch_tiles<true>(p, head_size, coop, grid, block, st);
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "paged_attention_prefill partition launch");
@@ -190,18 +209,12 @@ static int launch_pa_prefill(void* out, const void* query, const void* key_cache
     fill(p);
     p.scale_log2e = (scale * kv_scale) * 1.4426950408889634f;   // K's kv_scale rides in the score scale (x 1.0f is exact)
     p.kv_scale = kv_scale;                                       // V's in the final kv_scale / sum
-    if (head_size == 64)
-      hipLaunchKernelGGL(prefill::pa_prefill_fp8_kernel<64>, grid, block, 0, static_cast<hipStream_t>(stream), p);
-    else
-      hipLaunchKernelGGL(prefill::pa_prefill_fp8_kernel<128>, grid, block, 0, static_cast<hipStream_t>(stream), p);
+    launch_tiles<false>(p, head_size, coop, grid, block, st);
   } else {
     prefill::Params p;
     fill(p);
     p.scale_log2e = scale * 1.4426950408889634f;
-    if (head_size == 64)
-      hipLaunchKernelGGL(prefill::pa_prefill_kernel<64>, grid, block, 0, static_cast<hipStream_t>(stream), p);
-    else
-      hipLaunchKernelGGL(prefill::pa_prefill_kernel<128>, grid, block, 0, static_cast<hipStream_t>(stream), p);
+    launch_tiles<false>(p, head_size, coop, grid, block, st);
   }
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(e, "paged_attention_prefill launch");
@@ -276,4 +289,32 @@ extern "C" int vmi_paged_attention_prefill_split_fp8(
                                 block_tables, seq_lens, cu_q_lens, num_seqs, max_q_len, block_size, max_num_blocks_per_seq,
                                 q_stride, kv_block_stride, kv_head_stride, device, stream, true, kv_scale, max_seq_len,
                                 partition_tokens, workspace, workspace_bytes);
+}
+
+extern "C" int vmi_paged_attention_prefill_coop_f16(
+    void* out, const void* query, const void* key_cache, const void* value_cache,
+    int32_t num_tokens, int32_t num_heads, int32_t head_size, int32_t num_kv_heads, float scale,
+    const int32_t* block_tables, const int32_t* seq_lens, const int32_t* cu_q_lens,
+    int32_t num_seqs, int32_t max_q_len, int32_t block_size, int32_t max_num_blocks_per_seq,
+    int64_t q_stride, int64_t kv_block_stride, int64_t kv_head_stride, int32_t device, void* stream,
+    int32_t max_seq_len, int32_t partition_tokens, void* workspace, int64_t workspace_bytes) {
+  if (max_seq_len < 0) return vmi::fail(VMI_E_SHAPE, "paged_attention_prefill: negative max_seq_len=%d", max_seq_len);
+  return vmi::launch_pa_prefill(out, query, key_cache, value_cache, num_tokens, num_heads, head_size, num_kv_heads, scale,
+                                block_tables, seq_lens, cu_q_lens, num_seqs, max_q_len, block_size, max_num_blocks_per_seq,
+                                q_stride, kv_block_stride, kv_head_stride, device, stream, false, 1.0f, max_seq_len,
+                                partition_tokens, workspace, workspace_bytes, true);
+}
+
+extern "C" int vmi_paged_attention_prefill_coop_fp8(
+    void* out, const void* query, const void* key_cache, const void* value_cache,
+    int32_t num_tokens, int32_t num_heads, int32_t head_size, int32_t num_kv_heads, float scale,
+    const int32_t* block_tables, const int32_t* seq_lens, const int32_t* cu_q_lens,
+    int32_t num_seqs, int32_t max_q_len, int32_t block_size, int32_t max_num_blocks_per_seq,
+    int64_t q_stride, int64_t kv_block_stride, int64_t kv_head_stride, int32_t device, void* stream,
+    int32_t max_seq_len, int32_t partition_tokens, void* workspace, int64_t workspace_bytes, float kv_scale) {
+  if (max_seq_len < 0) return vmi::fail(VMI_E_SHAPE, "paged_attention_prefill: negative max_seq_len=%d", max_seq_len);
+  return vmi::launch_pa_prefill(out, query, key_cache, value_cache, num_tokens, num_heads, head_size, num_kv_heads, scale,
+                                block_tables, seq_lens, cu_q_lens, num_seqs, max_q_len, block_size, max_num_blocks_per_seq,
+                                q_stride, kv_block_stride, kv_head_stride, device, stream, true, kv_scale, max_seq_len,
+                                partition_tokens, workspace, workspace_bytes, true);
 }

@@ -9,7 +9,8 @@
 // Work split.  A wave owns a 16-row query tile of one (sequence, head); a workgroup is four waves = 64 consecutive rows.
 // The four tiles start together and walk the same K / V blocks from block 0 upwards, two blocks per trip, each straight
 // from global memory into MFMA operand registers — a block fetched by one wave is an L1 / L2 hit for the other three (no
-// LDS, no barrier: the tiles' trip counts differ by at most two, and a wave past its diagonal simply leaves).
+// LDS, no barrier: the tiles' trip counts differ by at most two, and a wave past its diagonal simply leaves).  The COOP form
+// (below) changes this for a group with ONE live tile only: its four waves share that tile's context and meet in LDS.
 //
 // Arithmetic per trip (a PAIR of 16-token blocks), everything transposed so that no operand ever changes lanes:
 //   S^T = K . Q^T    v_mfma_f32_16x16x32_f16, A = the K block exactly as it lies in the page ([D/8][16][8] halves: lane
@@ -95,6 +96,52 @@ __device__ __forceinline__ void store_partial(float* ws, int num_tokens, int num
   }
 }
 
+// The cooperative form's meeting point (COOP, below): the four waves of a workgroup hold partial triples (o, m, l) of ONE tile,
+// each over its own pairs of the context, in the SAME lanes — lane (n, kg) of every wave owns dims 16t + 4kg .. + 3 of query
+// column n, and m / l (after the cross-lane sum) are the column's in all four of its lanes.  So the merge needs no lane to
+// read another's slot: waves 1 - 3 write theirs, one barrier, wave 0 reads them back at its own lane index.
+// Layout, per writing wave: acc[t][lane] f32x4 — a ds_write_b128 / ds_read_b128 of 64 lanes covers 1 KiB contiguously, lane l
+// the bytes 16 l .. 16 l + 15: consecutive lanes on consecutive 16-byte slots, the order in which a 128-bit LDS access is
+// free of bank conflicts — then m[lane] and l[lane], consecutive dwords.  64 * (D / 4 + 2) * 4 bytes per wave: 13.5 KiB for
+// the three at D 64, 25.5 KiB at D 128.  Static, and only in the COOP instantiations.
+template <int D>
+struct CoopLds {
+  f32x4 acc[WAVES - 1][D / 16][64];
+  float m[WAVES - 1][64], l[WAVES - 1][64];
+};
+
+// EVERY wave of the workgroup calls this (one __syncthreads inside).  -> true in wave 0, whose (o, m, lsum) are then the merged
+// triple:  M = max_w m_w first, then  o = sum_w 2^(m_w - M) o_w,  l = sum_w 2^(m_w - M) l_w,  w ascending, fp32 — the
+// arithmetic of pa_prefill_merge_kernel, fixed order, nothing atomic.  A wave that walked no pair brings m = -3e38, l = 0,
+// o = 0: its weight is 2^(-huge) = 0 (or 2^0 on a column nobody saw, where every term is 0).
+template <int D>
+__device__ __forceinline__ bool coop_merge(CoopLds<D>& lds, int wave, int lane, f32x4 (&o)[D / 16], float& m, float& lsum) {
+  if (wave > 0) {
+#pragma unroll
+    for (int t = 0; t < D / 16; ++t) lds.acc[wave - 1][t][lane] = o[t];
+    lds.m[wave - 1][lane] = m;
+    lds.l[wave - 1][lane] = lsum;
+  }
+  __syncthreads();
+  if (wave > 0) return false;
+  float mw[WAVES - 1], M = m;
+#pragma unroll
+  for (int w = 0; w < WAVES - 1; ++w) M = fmaxf(M, mw[w] = lds.m[w][lane]);
+  float wgt = __builtin_amdgcn_exp2f(m - M);
+#pragma unroll
+  for (int t = 0; t < D / 16; ++t) o[t] *= wgt;
+  lsum *= wgt;
+#pragma unroll
+  for (int w = 0; w < WAVES - 1; ++w) {
+    wgt = __builtin_amdgcn_exp2f(mw[w] - M);
+#pragma unroll
+    for (int t = 0; t < D / 16; ++t) o[t] += lds.acc[w][t][lane] * wgt;
+    lsum += lds.l[w][lane] * wgt;
+  }
+  m = M;
+  return true;
+}
+
 // Grid: one workgroup per (64-row group, sequence, head), x = group_rev * (num_seqs * num_heads) + seq * num_heads + head.
 // group_rev counts a sequence's groups from its LAST one, so the first num_seqs * num_heads workgroups of the launch are
 // every sequence's longest causal range; a sequence with fewer groups than the host bound leaves the surplus at once.
@@ -107,7 +154,18 @@ __device__ __forceinline__ void store_partial(float* ws, int num_tokens, int num
 // all alike, and the lower a partition the more tiles own all of it — so the launch starts with the workgroups that all
 // work their full length, and those that leave at once (partitions past a sequence's end) come last.  Neighbours in x are
 // the heads of one sequence in one partition: the query heads of a KV head read the same pages at the same time.
-template <int D, bool SPLIT = false>
+//
+// COOP (the cooperative form, for a group of at most 16 live rows: a decode row, look-ahead rows, a chunk's tail, a 16-row
+// chunk): waves 1 - 3 of such a workgroup have no tile of their own, so all four take the group's ONE tile — same j0, pos,
+// last_pos and Q operand — and wave w walks the pairs pp0 + w, pp0 + w + 4, ... below pp1: interleaved, so that the four stay on
+// neighbouring pages and share the work evenly whatever the length.  The trip is the same code; each wave's double buffer
+// prefetches its OWN next pair, and the V clearing of pair npair - 1 happens in the wave that owns it.  They meet in
+// coop_merge(); wave 0 stores (normalised to `out`, or store_partial in the SPLIT form — grid, Params, workspace and merge
+// launch are the plain forms').  Whether a workgroup cooperates depends on (sequence, group) alone: it is workgroup-uniform,
+// and so is every return in front of the barrier on that path (guard, surplus group, partition past the tile — the four
+// waves share last_pos); the per-wave `j0 >= q_len` exit is not on it.  A group with more than 16 live rows runs exactly
+// the plain code: step 1 from pp0, no LDS access, no barrier — bit-identical results.
+template <int D, bool SPLIT = false, bool COOP = false>
 __global__ void __launch_bounds__(WAVES * 64) pa_prefill_kernel(const Params p) {
   constexpr int KC = D / 32;    // 32-dim chunks of a K block: one MFMA each
   constexpr int VT = D / 16;    // 16-dim tiles of the output: one MFMA each
@@ -124,8 +182,13 @@ __global__ void __launch_bounds__(WAVES * 64) pa_prefill_kernel(const Params p) 
   const int ctx = L - q_len;    // cached positions in front of the chunk
   const int ngroups = (q_len + ROWS - 1) / ROWS;
   if (grev >= ngroups) return;
-  const int j0 = ((ngroups - 1 - grev) * WAVES + wave) * TILE;   // first row of my tile within the chunk
-  if (j0 >= q_len) return;                                        // (wave-uniform)
+  int j0 = ((ngroups - 1 - grev) * WAVES + wave) * TILE;         // first row of my tile within the chunk
+  bool coop = false;                                              // (workgroup-uniform)
+  if constexpr (COOP) {
+    coop = q_len - (ngroups - 1 - grev) * ROWS <= TILE;           // my group's live rows fit one tile: all four waves take it
+    if (coop) j0 = (ngroups - 1 - grev) * ROWS;
+  }
+  if (!coop && j0 >= q_len) return;                               // (wave-uniform; never taken by a cooperating workgroup)
 
   const int n = lane & 15, kg = lane >> 4;
   const int jr = min(j0 + n, q_len - 1);                 // rows past the chunk repeat its last row and are not stored
@@ -135,7 +198,7 @@ __global__ void __launch_bounds__(WAVES * 64) pa_prefill_kernel(const Params p) 
   // the trips I walk: all of them, or my partition's (it starts on a pair boundary; a tile that ends below it leaves)
   int pp0 = 0, pp1 = npair;
   if constexpr (SPLIT) {
-    if (last_pos < part * p.part_tokens) return;           // (wave-uniform)
+    if (last_pos < part * p.part_tokens) return;           // (wave-uniform; workgroup-uniform when cooperating)
     pp0 = part * (p.part_tokens >> 5);
     pp1 = min(npair, pp0 + (p.part_tokens >> 5));
   }
@@ -179,10 +242,20 @@ __global__ void __launch_bounds__(WAVES * 64) pa_prefill_kernel(const Params p) 
 
   h16x8 kcur[2][KC], knext[2][KC];
   u32x2 v[2][VT];
-  load_k(kcur, pp0);
-  for (int pp = pp0; pp < pp1; ++pp) {
+  // my trips: every pair of [pp0, pp1), or — cooperating — every fourth from pp0 + wave (none at all: the loop is skipped,
+  // the load in front of it re-reads the tile's last block)
+  int step = 1, first = pp0, last = pp1 - 1;
+  if constexpr (COOP) {
+    if (coop) {
+      step = WAVES;
+      first = pp0 + wave;
+      last = first + (pp1 - 1 - first) / WAVES * WAVES;   // my last pair (unused when I have none)
+    }
+  }
+  load_k(kcur, first);
+  for (int pp = first; pp < pp1; pp += step) {
     load_v(v, pp);
-    load_k(knext, min(pp + 1, pp1 - 1));   // (the last trip re-reads its own pair: no branch around the loads)
+    load_k(knext, min(pp + step, last));   // (my last trip re-reads its own pair: no branch around the loads)
 
     // ---- S^T = K . Q^T, scaled in fp32, causal mask selected ----
     float s[2][4];
@@ -243,6 +316,12 @@ __global__ void __launch_bounds__(WAVES * 64) pa_prefill_kernel(const Params p) 
 
   lsum += __shfl_xor(lsum, 16);
   lsum += __shfl_xor(lsum, 32);
+  if constexpr (COOP) {
+    if (coop) {   // all four waves are here: none left through a per-wave exit
+      __shared__ CoopLds<D> lds;
+      if (!coop_merge<D>(lds, wave, lane, o, m, lsum)) return;
+    }
+  }
   if constexpr (SPLIT) {
     // unnormalised partials of the columns that see a token of this partition (the others hold sum 0 and are never merged)
     if (j0 + n < q_len && pos >= part * p.part_tokens)

@@ -21,7 +21,8 @@
 //   kv_scale         no instruction per element: K's factor rides in the score scale (scale * kv_scale * log2 e on the fp32
 //                    scores, folded on the host), V's in the final kv_scale / sum.  kv_scale == 1 multiplies by 1.0f: exact.
 //   pipelining       the fp16 kernel's register double buffer, on raw bytes: the next pair's K and this pair's V (D/8 dwords
-//                    each) are in flight during the MFMAs; decoding happens at use.  No LDS, no barrier.
+//                    each) are in flight during the MFMAs; decoding happens at use.  No LDS, no barrier — but for the
+//                    COOP form's one meeting of a short tile's four waves (coop_merge, pa_prefill.hpp).
 #pragma once
 
 #include "pa_prefill.hpp"
@@ -58,8 +59,10 @@ __device__ __forceinline__ h16x8 e4m3x8_to_h16x8(uint32_t w0, uint32_t w1) {
 }
 
 // Grid: as pa_prefill_kernel — x = group_rev * (num_seqs * num_heads) + seq * num_heads + head; SPLIT: its partition form
-// (partition outer, store_partial() instead of the normalised store; V partials leave WITHOUT kv_scale: the merge applies it).
-template <int D, bool SPLIT = false>
+// (partition outer, store_partial() instead of the normalised store; V partials leave WITHOUT kv_scale: the merge applies it);
+// COOP: its cooperative form (a group of at most 16 live rows is walked by all four waves, pairs interleaved, merged in LDS
+// on the still unscaled triples; the barrier rule is written there).
+template <int D, bool SPLIT = false, bool COOP = false>
 __global__ void __launch_bounds__(WAVES * 64) pa_prefill_fp8_kernel(const ParamsFp8 p) {
   constexpr int KG = D / 64;    // 64-dim groups of a K block: one 16-byte load, two MFMAs each
   constexpr int VT = D / 16;    // 16-dim tiles of the output: one dword per block, one MFMA each
@@ -76,8 +79,13 @@ __global__ void __launch_bounds__(WAVES * 64) pa_prefill_fp8_kernel(const Params
   const int ctx = L - q_len;    // cached positions in front of the chunk
   const int ngroups = (q_len + ROWS - 1) / ROWS;
   if (grev >= ngroups) return;
-  const int j0 = ((ngroups - 1 - grev) * WAVES + wave) * TILE;   // first row of my tile within the chunk
-  if (j0 >= q_len) return;                                        // (wave-uniform)
+  int j0 = ((ngroups - 1 - grev) * WAVES + wave) * TILE;         // first row of my tile within the chunk
+  bool coop = false;                                              // (workgroup-uniform)
+  if constexpr (COOP) {
+    coop = q_len - (ngroups - 1 - grev) * ROWS <= TILE;           // my group's live rows fit one tile: all four waves take it
+    if (coop) j0 = (ngroups - 1 - grev) * ROWS;
+  }
+  if (!coop && j0 >= q_len) return;                               // (wave-uniform; never taken by a cooperating workgroup)
 
   const int n = lane & 15, kg = lane >> 4;
   const int jr = min(j0 + n, q_len - 1);                 // rows past the chunk repeat its last row and are not stored
@@ -87,7 +95,7 @@ __global__ void __launch_bounds__(WAVES * 64) pa_prefill_fp8_kernel(const Params
   // the trips I walk: all of them, or my partition's (it starts on a pair boundary; a tile that ends below it leaves)
   int pp0 = 0, pp1 = npair;
   if constexpr (SPLIT) {
-    if (last_pos < part * p.part_tokens) return;           // (wave-uniform)
+    if (last_pos < part * p.part_tokens) return;           // (wave-uniform; workgroup-uniform when cooperating)
     pp0 = part * (p.part_tokens >> 5);
     pp1 = min(npair, pp0 + (p.part_tokens >> 5));
   }
@@ -134,10 +142,19 @@ __global__ void __launch_bounds__(WAVES * 64) pa_prefill_fp8_kernel(const Params
 
   u32x4 kcur[2][KG], knext[2][KG];
   uint32_t v[2][VT];
-  load_k(kcur, pp0);
-  for (int pp = pp0; pp < pp1; ++pp) {
+  // my trips: every pair of [pp0, pp1), or — cooperating — every fourth from pp0 + wave (none at all: the loop is skipped)
+  int step = 1, first = pp0, last = pp1 - 1;
+  if constexpr (COOP) {
+    if (coop) {
+      step = WAVES;
+      first = pp0 + wave;
+      last = first + (pp1 - 1 - first) / WAVES * WAVES;   // my last pair (unused when I have none)
+    }
+  }
+  load_k(kcur, first);
+  for (int pp = first; pp < pp1; pp += step) {
     load_v(v, pp);
-    load_k(knext, min(pp + 1, pp1 - 1));   // (the last trip re-reads its own pair: no branch around the loads)
+    load_k(knext, min(pp + step, last));   // (my last trip re-reads its own pair: no branch around the loads)
 
     // ---- S^T = K . Q^T, scaled in fp32 (kv_scale included), causal mask selected ----
     float s[2][4];
@@ -199,6 +216,12 @@ __global__ void __launch_bounds__(WAVES * 64) pa_prefill_fp8_kernel(const Params
 
   lsum += __shfl_xor(lsum, 16);
   lsum += __shfl_xor(lsum, 32);
+  if constexpr (COOP) {
+    if (coop) {   // all four waves are here: none left through a per-wave exit
+      __shared__ CoopLds<D> lds;
+      if (!coop_merge<D>(lds, wave, lane, o, m, lsum)) return;
+    }
+  }
   if constexpr (SPLIT) {
     // unnormalised partials of the columns that see a token of this partition (the others hold sum 0 and are never merged)
     if (j0 + n < q_len && pos >= part * p.part_tokens)

@@ -507,6 +507,32 @@ def prefill_split_plan(num_tokens: int, num_heads: int, head_size: int, num_seqs
     return pt.value, parts.value, nbytes.value
 
 
+# cooperative=None, read off profiles/prefill_coop.md section 2 (MI355X, 256 CUs): the cooperative launch is taken for chunks
+# of at most 16 rows from this max_seq_len on (the smallest measured context from which it wins beyond the ranges' overlap,
+# in both page formats) ...
+PREFILL_COOP_MIN_CONTEXT = 512
+# ... while the grid has at most this many workgroups per CU, as (numerator, denominator): the fullest measured grid on which it
+# wins in both formats.  At 3 per CU the float16 launch is bound by memory bandwidth and the form gains nothing there.
+PREFILL_COOP_MAX_WGS_PER_CU = (3, 2)
+
+
+def _num_cus(index: int) -> int:
+    cus = _NUM_CUS.get(index)
+    if cus is None:
+        cus = _NUM_CUS[index] = int(torch.cuda.get_device_properties(index).multi_processor_count)
+    return cus
+
+
+def prefill_cooperative_for(max_q_len: int, max_seq_len: Optional[int], num_seqs: int, num_heads: int, num_cus: int) -> bool:
+    """What paged_attention_prefill(cooperative=None) resolves to, from host-known bounds alone: the cooperative launch when
+    no sequence has more than 16 rows (every workgroup then holds one live tile), max_seq_len is given and at least
+    PREFILL_COOP_MIN_CONTEXT, and the num_seqs * num_heads workgroups leave the chip's SIMDs underfilled
+    (PREFILL_COOP_MAX_WGS_PER_CU).  Measurements: profiles/prefill_coop.md."""
+    num, den = PREFILL_COOP_MAX_WGS_PER_CU
+    return max_seq_len is not None and 0 < int(max_q_len) <= 16 and int(max_seq_len) >= PREFILL_COOP_MIN_CONTEXT and \
+        den * int(num_seqs) * int(num_heads) <= num * int(num_cus)
+
+
 def paged_attention_prefill(
     out: torch.Tensor,
     query: torch.Tensor,
@@ -523,6 +549,7 @@ def paged_attention_prefill(
     kv_scale: float = 1.0,
     max_seq_len: Optional[int] = None,
     partition_tokens: Optional[int] = None,
+    cooperative: Optional[bool] = False,
 ) -> None:
     """Tiled causal attention of a chunk of query rows per sequence over the paged cache (extension: the reference runs its
     prefill as eager masked attention, gpt2.py:46-58); writes `out` in place, returns None.
@@ -540,7 +567,15 @@ def paged_attention_prefill(
     context that meet in a wrapper-owned workspace (prefill_workspace_for) and a merge launch.  The library's rule decides
     from the host-known bounds whether and how finely (prefill_split_plan; profiles/prefill_split.md); `partition_tokens` (a
     multiple of 32, needs max_seq_len) forces the size, for tests and tuning.  A sequence longer than max_seq_len writes
-    nothing.  Under stream capture with no cached workspace large enough, the single launch is taken."""
+    nothing.  Under stream capture with no cached workspace large enough, the single launch is taken.
+
+    `cooperative` picks the COOPERATIVE form of the tile kernels: in a 64-row group with at most 16 live rows (a decode row,
+    look-ahead rows, a chunk's tail, a 16-row chunk) the workgroup's four waves share the one tile's context and merge in LDS,
+    where the plain form leaves three of them idle; groups with more live rows compute bit for bit what the plain form does.
+    False (default): the plain launches.  True: the cooperative ones, split or not as above (without max_seq_len the block
+    table's capacity stands in as the bound).  None: the measured rule, prefill_cooperative_for — never without max_seq_len."""
+    if cooperative is not None and not isinstance(cooperative, bool):
+        raise RuntimeError(f"paged_attention_prefill: cooperative must be True, False or None, got {cooperative!r}")
     if max_seq_len is None and partition_tokens is not None:
         raise RuntimeError("paged_attention_prefill: partition_tokens needs max_seq_len (the host-known bound on seq_lens)")
     fp8 = _check_kv_cache_dtype(kv_cache_dtype)     # first: an unknown or unbuilt dtype is reported whatever the tensors are
@@ -611,20 +646,26 @@ def paged_attention_prefill(
             block_tables.data_ptr(), seq_lens.data_ptr(), cu_q_lens.data_ptr(),
             num_seqs, int(max_q_len), block_size, ts[1], qst[0], kst[0], kst[1], index, _stream_of(index))
     lib = _lib.load()
-    if max_seq_len is not None:
-        cus = _NUM_CUS.get(index)
-        if cus is None:
-            cus = _NUM_CUS[index] = int(torch.cuda.get_device_properties(index).multi_processor_count)
-        pt, parts, nbytes = prefill_split_plan(num_tokens, num_heads, head_size, num_seqs, max_q_len, max_seq_len, cus,
-                                               int(partition_tokens or 0))
+    coop = cooperative
+    if coop is None:
+        coop = max_seq_len is not None and prefill_cooperative_for(max_q_len, max_seq_len, num_seqs, num_heads, _num_cus(index))
+    if coop and max_seq_len is None:                    # one cooperative launch, bounded by what the block table can hold
+        bound = min(16 * ts[1], 2 ** 31 - 32)
+        tail = (bound, max(32, (bound + 31) // 32 * 32), None, 0)
+        rc = lib.vmi_paged_attention_prefill_coop_fp8(*args, *tail, float(kv_scale)) if fp8 else \
+            lib.vmi_paged_attention_prefill_coop_f16(*args, *tail)
+    elif max_seq_len is not None:
+        pt, parts, nbytes = prefill_split_plan(num_tokens, num_heads, head_size, num_seqs, max_q_len, max_seq_len,
+                                               _num_cus(index), int(partition_tokens or 0))
         ws = prefill_workspace_for(index, nbytes, args[-1]) if parts > 1 else None
         if ws is None:                                  # one partition (or capturing without a workspace): the single launch
             pt, ws_ptr, ws_len = max(32, (int(max_seq_len) + 31) // 32 * 32), None, 0
         else:
             ws_ptr, ws_len = ws.data_ptr(), ws.numel()
         tail = (int(max_seq_len), pt, ws_ptr, ws_len)
-        rc = lib.vmi_paged_attention_prefill_split_fp8(*args, *tail, float(kv_scale)) if fp8 else \
-            lib.vmi_paged_attention_prefill_split_f16(*args, *tail)
+        form = "coop" if coop else "split"
+        rc = getattr(lib, f"vmi_paged_attention_prefill_{form}_fp8")(*args, *tail, float(kv_scale)) if fp8 else \
+            getattr(lib, f"vmi_paged_attention_prefill_{form}_f16")(*args, *tail)
     elif fp8:
         rc = lib.vmi_paged_attention_prefill_fp8(*args, float(kv_scale))
     else:
