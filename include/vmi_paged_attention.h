@@ -506,6 +506,47 @@ int vmi_paged_attention_prefill_coop_fp8(
     int32_t max_seq_len, int32_t partition_tokens, void* workspace, int64_t workspace_bytes, float kv_scale);
 
 /*
+ * The same operator in its HEAD-PACKED form (added under ABI 22 like the entries above): for short chunks of grouped-query
+ * attention — a decode row, look-ahead or verification rows, a chunk's tail on G = num_heads / num_kv_heads query heads per KV
+ * head — where the forms above give every 16-column tile to ONE query head, so that each of the G heads walks the same pages
+ * in a workgroup of its own with q_len of 16 columns live.  Here the 16 columns of a tile are (row, query head of one KV head)
+ * pairs, head-minor: column n is row (n / G) of the tile and head kv_head * G + n % G; a tile is 16 / G rows x G heads, one
+ * per workgroup, and the grid runs over ceil(max_q_len / (16 / G)) tiles x num_seqs x num_kv_heads (x partitions): the pages
+ * are fetched (and, fp8, decoded) once per KV head.  The workgroup's four waves always share the tile's context as in the
+ * cooperative form — pairs of blocks interleaved, one meeting in LDS, fixed order, no atomics: run-to-run bit-identical, and
+ * on a sequence of at most 16 / G rows bit for bit what vmi_paged_attention_prefill_coop_* computes.
+ * Kernels: the PACK form in vllmini_amd/csrc/pa_prefill.hpp / pa_prefill_fp8.hpp.
+ * Arguments and validation are vmi_paged_attention_prefill_coop_f16's / _fp8's (one partition: one launch, workspace may be
+ * NULL; more: the packed partition kernels and the same merge launch over the same workspace layout), and in addition:
+ *   num_heads / num_kv_heads   must be 2, 4, 8 or 16, else VMI_E_KV_HEADS (the message names the ratio) — in front of any HIP call.
+ */
+int vmi_paged_attention_prefill_gqa_f16(
+    void* out, const void* query, const void* key_cache, const void* value_cache,
+    int32_t num_tokens, int32_t num_heads, int32_t head_size, int32_t num_kv_heads, float scale,
+    const int32_t* block_tables, const int32_t* seq_lens, const int32_t* cu_q_lens,
+    int32_t num_seqs, int32_t max_q_len, int32_t block_size, int32_t max_num_blocks_per_seq,
+    int64_t q_stride, int64_t kv_block_stride, int64_t kv_head_stride, int32_t device, void* stream,
+    int32_t max_seq_len, int32_t partition_tokens, void* workspace, int64_t workspace_bytes);
+int vmi_paged_attention_prefill_gqa_fp8(
+    void* out, const void* query, const void* key_cache, const void* value_cache,
+    int32_t num_tokens, int32_t num_heads, int32_t head_size, int32_t num_kv_heads, float scale,
+    const int32_t* block_tables, const int32_t* seq_lens, const int32_t* cu_q_lens,
+    int32_t num_seqs, int32_t max_q_len, int32_t block_size, int32_t max_num_blocks_per_seq,
+    int64_t q_stride, int64_t kv_block_stride, int64_t kv_head_stride, int32_t device, void* stream,
+    int32_t max_seq_len, int32_t partition_tokens, void* workspace, int64_t workspace_bytes, float kv_scale);
+
+/*
+ * Plan of the head-packed launch: vmi_paged_attention_prefill_split_plan's arguments, results and rule (same constants), but the
+ * grid it counts against num_cus is the packed one, ceil(max_q_len / (16 / G)) * num_seqs * num_kv_heads workgroups.  The
+ * workspace is indexed by (row, head) as before: workspace_bytes is the same num_partitions * num_tokens * num_heads *
+ * (head_size + 2) * 4.  A ratio outside {2, 4, 8, 16} answers VMI_E_KV_HEADS.
+ */
+int vmi_paged_attention_prefill_gqa_plan(
+    int32_t num_tokens, int32_t num_heads, int32_t head_size, int32_t num_seqs, int32_t max_q_len, int32_t max_seq_len,
+    int32_t num_cus, int32_t partition_tokens_in, int32_t* partition_tokens, int32_t* num_partitions,
+    int64_t* workspace_bytes, int32_t num_kv_heads);
+
+/*
  * The pool's preemption move (extension; counterpart of BlockManager.swap_to_cpu / swap_from_cpu,
  * vllmini/block_manager.py:70-87, which the reference runs as one copy per block, cache_kernels.cu:56-62): ONE launch on
  * `stream` moves block_mapping[i] = (src block, dst block) of BOTH caches for every i.

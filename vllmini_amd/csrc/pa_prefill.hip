@@ -27,10 +27,24 @@ struct SplitRules {
 };
 static constexpr SplitRules kSplitRules = {2, 4096, 3, 32, 512, 2048};
 
-// -> VMI_OK and (partition_tokens, num_partitions, workspace_bytes); num_partitions == 1: do not split, 0 bytes
+// The head-packed form's ratio G = num_heads / num_kv_heads: -> log2 G for G in {2, 4, 8, 16}, -1 otherwise
+static int pack_shift(int32_t num_heads, int32_t num_kv_heads) {
+  if (num_kv_heads <= 0 || num_heads <= 0 || num_heads % num_kv_heads != 0) return -1;
+  const int g = num_heads / num_kv_heads;
+  return g == 2 ? 1 : g == 4 ? 2 : g == 8 ? 3 : g == 16 ? 4 : -1;
+}
+static int fail_pack_ratio(int32_t num_heads, int32_t num_kv_heads) {
+  if (num_kv_heads > 0 && num_heads > 0 && num_heads % num_kv_heads == 0)
+    return fail(VMI_E_KV_HEADS, "paged_attention_prefill: the head-packed form is built for num_heads / num_kv_heads in "
+                "{2, 4, 8, 16}, got ratio %d (num_heads=%d num_kv_heads=%d)", num_heads / num_kv_heads, num_heads, num_kv_heads);
+  return fail(VMI_E_KV_HEADS, "paged_attention_prefill: num_heads=%d not divisible by num_kv_heads=%d", num_heads, num_kv_heads);
+}
+
+// -> VMI_OK and (partition_tokens, num_partitions, workspace_bytes); num_partitions == 1: do not split, 0 bytes.
+// g_shift >= 0: the head-packed grid — ceil(max_q_len / R) tiles of R = 16 >> g_shift rows per (sequence, KV head)
 static int split_plan(int32_t num_tokens, int32_t num_heads, int32_t head_size, int32_t num_seqs, int32_t max_q_len,
                       int32_t max_seq_len, int32_t num_cus, int32_t partition_tokens_in, int32_t* partition_tokens,
-                      int32_t* num_partitions, int64_t* workspace_bytes) {
+                      int32_t* num_partitions, int64_t* workspace_bytes, int g_shift = -1) {
   if (num_tokens < 0 || num_heads <= 0 || num_seqs < 0 || max_q_len < 0 || max_seq_len < 0 || num_cus <= 0)
     return fail(VMI_E_SHAPE, "paged_attention_prefill_split_plan: negative size (num_tokens=%d num_heads=%d num_seqs=%d "
                 "max_q_len=%d max_seq_len=%d num_cus=%d)", num_tokens, num_heads, num_seqs, max_q_len, max_seq_len, num_cus);
@@ -42,7 +56,8 @@ static int split_plan(int32_t num_tokens, int32_t num_heads, int32_t head_size, 
   int64_t pt = partition_tokens_in;
   if (pt == 0) {
     const SplitRules& r = kSplitRules;
-    const int64_t wgs = (((int64_t)max_q_len + prefill::ROWS - 1) / prefill::ROWS) * num_seqs * num_heads;
+    const int64_t rows = g_shift < 0 ? prefill::ROWS : prefill::TILE >> g_shift;   // chunk rows per workgroup
+    const int64_t wgs = (((int64_t)max_q_len + rows - 1) / rows) * num_seqs * (g_shift < 0 ? num_heads : num_heads >> g_shift);
     pt = max_seq_len > 32 ? ((int64_t)max_seq_len + 31) & ~31ll : 32;   // one partition
     if (wgs > 0 && wgs < (int64_t)r.underfill_wgs_per_cu * num_cus && max_seq_len >= r.min_context) {
       int64_t parts = ((int64_t)r.target_wgs_per_cu * num_cus + wgs - 1) / wgs;
@@ -58,7 +73,8 @@ static int split_plan(int32_t num_tokens, int32_t num_heads, int32_t head_size, 
   return VMI_OK;
 }
 
-// The tile kernel of (page format by the Params type, head size, form): one place for the twelve instantiations
+// The tile kernel of (page format by the Params type, head size, form): one place for the sixteen instantiations, and below
+// it the eight of the head-packed form
 template <bool SPLIT, bool COOP>
 static void launch_tiles(const prefill::Params& p, int head_size, dim3 grid, dim3 block, hipStream_t st) {
   if (head_size == 64)
@@ -73,16 +89,33 @@ static void launch_tiles(const prefill::ParamsFp8& p, int head_size, dim3 grid, 
   else
     hipLaunchKernelGGL((prefill::pa_prefill_fp8_kernel<128, SPLIT, COOP>), grid, block, 0, st, p);
 }
+template <bool SPLIT>
+static void launch_packed(const prefill::Params& p, int head_size, dim3 grid, dim3 block, hipStream_t st) {
+  if (head_size == 64)
+    hipLaunchKernelGGL((prefill::pa_prefill_kernel<64, SPLIT, true, true>), grid, block, 0, st, p);
+  else
+    hipLaunchKernelGGL((prefill::pa_prefill_kernel<128, SPLIT, true, true>), grid, block, 0, st, p);
+}
+template <bool SPLIT>
+static void launch_packed(const prefill::ParamsFp8& p, int head_size, dim3 grid, dim3 block, hipStream_t st) {
+  if (head_size == 64)
+    hipLaunchKernelGGL((prefill::pa_prefill_fp8_kernel<64, SPLIT, true, true>), grid, block, 0, st, p);
+  else
+    hipLaunchKernelGGL((prefill::pa_prefill_fp8_kernel<128, SPLIT, true, true>), grid, block, 0, st, p);
+}
 template <bool SPLIT, class P>
 static void launch_tiles(const P& p, int head_size, bool coop, dim3 grid, dim3 block, hipStream_t st) {
-  if (coop)
+  if (p.g_shift >= 0)
+    launch_packed<SPLIT>(p, head_size, grid, block, st);
+  else if (coop)
     launch_tiles<SPLIT, true>(p, head_size, grid, block, st);
   else
     launch_tiles<SPLIT, false>(p, head_size, grid, block, st);
 }
 
 // max_seq_len < 0: the plain entries — never split, no bound on seq_lens.  coop: the cooperative form of the tile kernels
-// (pa_prefill.hpp, COOP) — same grid, same Params, same merge launch.
+// (pa_prefill.hpp, COOP) — same grid, same Params, same merge launch.  pack: the head-packed form (PACK) — one tile of
+// 16 / G rows x G heads per workgroup, a grid over KV heads; Params, workspace and merge launch are the same again.
 static int launch_pa_prefill(void* out, const void* query, const void* key_cache, const void* value_cache,
                              int32_t num_tokens, int32_t num_heads, int32_t head_size, int32_t num_kv_heads, float scale,
                              const int32_t* block_tables, const int32_t* seq_lens, const int32_t* cu_q_lens,
@@ -90,7 +123,7 @@ static int launch_pa_prefill(void* out, const void* query, const void* key_cache
                              int64_t q_stride, int64_t kv_block_stride, int64_t kv_head_stride, int32_t device,
                              void* stream, bool fp8, float kv_scale, int32_t max_seq_len = -1,
                              int32_t partition_tokens = 0, void* workspace = nullptr, int64_t workspace_bytes = 0,
-                             bool coop = false) {
+                             bool coop = false, bool pack = false) {
   // one validation for both page formats; the cache strides are in cache elements: halves, or bytes when fp8
   const bool empty = num_tokens == 0 || num_seqs == 0;   // (torch hands out null data pointers for empty tensors)
   if (!key_cache || !value_cache || (!empty && (!out || !query || !block_tables || !seq_lens || !cu_q_lens)))
@@ -107,6 +140,8 @@ static int launch_pa_prefill(void* out, const void* query, const void* key_cache
   if (num_kv_heads <= 0 || num_heads % num_kv_heads != 0)
     return fail(VMI_E_KV_HEADS, "paged_attention_prefill: num_heads=%d not divisible by num_kv_heads=%d", num_heads,
                 num_kv_heads);
+  const int g_shift = pack ? pack_shift(num_heads, num_kv_heads) : -1;
+  if (pack && g_shift < 0) return fail_pack_ratio(num_heads, num_kv_heads);
   const int64_t kv_mask = fp8 ? 15 : 7;   // 16 bytes in cache elements
   if (!aligned16(query) || !aligned16(key_cache) || !aligned16(value_cache) || (reinterpret_cast<uintptr_t>(out) & 7u) ||
       (q_stride & 7) || (kv_block_stride & kv_mask) || (kv_head_stride & kv_mask))
@@ -131,8 +166,9 @@ static int launch_pa_prefill(void* out, const void* query, const void* key_cache
                   parts, (long long)need, workspace, (long long)workspace_bytes);
   }
   if (empty || max_q_len == 0 || max_seq_len == 0) return VMI_OK;
-  const int64_t groups = ((int64_t)max_q_len + prefill::ROWS - 1) / prefill::ROWS;
-  const int64_t wgs = groups * num_seqs * num_heads * parts;
+  const int64_t tile_rows = pack ? prefill::TILE >> g_shift : prefill::ROWS;   // chunk rows per workgroup
+  const int64_t groups = ((int64_t)max_q_len + tile_rows - 1) / tile_rows;
+  const int64_t wgs = groups * num_seqs * (pack ? num_kv_heads : num_heads) * parts;
   constexpr int MERGE_ROWS = 1024 / 128;                  // the merge's rows per workgroup at its smallest (D 128)
   if ((int64_t)num_seqs * num_heads >= (1ll << 31) || wgs >= (1ll << 31) ||
       (parts > 1 && ((int64_t)max_q_len + MERGE_ROWS - 1) / MERGE_ROWS * num_seqs * num_heads >= (1ll << 31)))
@@ -159,6 +195,7 @@ static int launch_pa_prefill(void* out, const void* query, const void* key_cache
     p.part_tokens = partition_tokens;
     p.num_parts = parts;
     p.groups = (int32_t)groups;
+    p.g_shift = g_shift;
   };
 
   DeviceGuard guard(device);
@@ -317,4 +354,52 @@ extern "C" int vmi_paged_attention_prefill_coop_fp8(
                                 block_tables, seq_lens, cu_q_lens, num_seqs, max_q_len, block_size, max_num_blocks_per_seq,
                                 q_stride, kv_block_stride, kv_head_stride, device, stream, true, kv_scale, max_seq_len,
                                 partition_tokens, workspace, workspace_bytes, true);
+}
+
+extern "C" int vmi_paged_attention_prefill_gqa_plan(
+    int32_t num_tokens, int32_t num_heads, int32_t head_size, int32_t num_seqs, int32_t max_q_len, int32_t max_seq_len,
+    int32_t num_cus, int32_t partition_tokens_in, int32_t* partition_tokens, int32_t* num_partitions,
+    int64_t* workspace_bytes, int32_t num_kv_heads) {
+  if (!partition_tokens || !num_partitions || !workspace_bytes)
+    return vmi::fail(VMI_E_NULL_POINTER, "paged_attention_prefill_gqa_plan: NULL result pointer");
+  const int g_shift = vmi::pack_shift(num_heads, num_kv_heads);
+  if (g_shift < 0) return vmi::fail_pack_ratio(num_heads, num_kv_heads);
+  if (num_cus == 0) {   // ask the current device
+    int dev = 0;
+    hipDeviceProp_t prop;
+    hipError_t e = hipGetDevice(&dev);
+    if (e == hipSuccess) e = hipGetDeviceProperties(&prop, dev);
+    if (e != hipSuccess) return vmi::hip_fail(e, "paged_attention_prefill_gqa_plan: device properties");
+    num_cus = prop.multiProcessorCount;
+  }
+  return vmi::split_plan(num_tokens, num_heads, head_size, num_seqs, max_q_len, max_seq_len, num_cus, partition_tokens_in,
+                         partition_tokens, num_partitions, workspace_bytes, g_shift);
+}
+
+extern "C" int vmi_paged_attention_prefill_gqa_f16(
+    void* out, const void* query, const void* key_cache, const void* value_cache,
+    int32_t num_tokens, int32_t num_heads, int32_t head_size, int32_t num_kv_heads, float scale,
+    const int32_t* block_tables, const int32_t* seq_lens, const int32_t* cu_q_lens,
+    int32_t num_seqs, int32_t max_q_len, int32_t block_size, int32_t max_num_blocks_per_seq,
+    int64_t q_stride, int64_t kv_block_stride, int64_t kv_head_stride, int32_t device, void* stream,
+    int32_t max_seq_len, int32_t partition_tokens, void* workspace, int64_t workspace_bytes) {
+  if (max_seq_len < 0) return vmi::fail(VMI_E_SHAPE, "paged_attention_prefill: negative max_seq_len=%d", max_seq_len);
+  return vmi::launch_pa_prefill(out, query, key_cache, value_cache, num_tokens, num_heads, head_size, num_kv_heads, scale,
+                                block_tables, seq_lens, cu_q_lens, num_seqs, max_q_len, block_size, max_num_blocks_per_seq,
+                                q_stride, kv_block_stride, kv_head_stride, device, stream, false, 1.0f, max_seq_len,
+                                partition_tokens, workspace, workspace_bytes, true, true);
+}
+
+extern "C" int vmi_paged_attention_prefill_gqa_fp8(
+    void* out, const void* query, const void* key_cache, const void* value_cache,
+    int32_t num_tokens, int32_t num_heads, int32_t head_size, int32_t num_kv_heads, float scale,
+    const int32_t* block_tables, const int32_t* seq_lens, const int32_t* cu_q_lens,
+    int32_t num_seqs, int32_t max_q_len, int32_t block_size, int32_t max_num_blocks_per_seq,
+    int64_t q_stride, int64_t kv_block_stride, int64_t kv_head_stride, int32_t device, void* stream,
+    int32_t max_seq_len, int32_t partition_tokens, void* workspace, int64_t workspace_bytes, float kv_scale) {
+  if (max_seq_len < 0) return vmi::fail(VMI_E_SHAPE, "paged_attention_prefill: negative max_seq_len=%d", max_seq_len);
+  return vmi::launch_pa_prefill(out, query, key_cache, value_cache, num_tokens, num_heads, head_size, num_kv_heads, scale,
+                                block_tables, seq_lens, cu_q_lens, num_seqs, max_q_len, block_size, max_num_blocks_per_seq,
+                                q_stride, kv_block_stride, kv_head_stride, device, stream, true, kv_scale, max_seq_len,
+                                partition_tokens, workspace, workspace_bytes, true, true);
 }

@@ -66,6 +66,8 @@ struct Params {
   // the partition form only (SPLIT, see below)
   float* ws;                    // partials: [parts][num_tokens][num_heads][D] fp32, then [parts][num_tokens][num_heads][2]
   int32_t part_tokens, num_parts, groups;   // tokens per context partition (a multiple of 32), partitions, the host's bound on 64-row groups
+  // the head-packed form only (PACK, see below), where `groups` is the host's bound on R-row tiles
+  int32_t g_shift;              // log2 G, G = q_per_kv in {2, 4, 8, 16}
 };
 
 // THE guard of every kernel of the operator (unsplit, partition form, merge): a sequence with nothing to do, or with
@@ -165,35 +167,53 @@ __device__ __forceinline__ bool coop_merge(CoopLds<D>& lds, int wave, int lane, 
 // and so is every return in front of the barrier on that path (guard, surplus group, partition past the tile — the four
 // waves share last_pos); the per-wave `j0 >= q_len` exit is not on it.  A group with more than 16 live rows runs exactly
 // the plain code: step 1 from pp0, no LDS access, no barrier — bit-identical results.
-template <int D, bool SPLIT = false, bool COOP = false>
+//
+// PACK (the head-packed form, for short chunks of grouped-query attention, G = q_per_kv in {2, 4, 8, 16}): the 16 columns of a
+// tile are (row, query head of ONE KV head) pairs, head-minor — column n is row j0 + (n >> log2 G) of the chunk and query head
+// kvh * G + (n & (G - 1)) — so a tile is R = 16 / G rows x the G heads that read the same pages: one walk of the context per KV
+// head instead of one per query head, and full tiles from q_len * G = 16 on.  Softmax, causal selection (each column's own
+// pos), rescale and 1 / sum are per column already; what changes is the column's (row, head) in the Q address, in jr / pos /
+// last_pos, in the liveness test and in the two stores — columns of one row are adjacent heads, neighbours in `out` and in the
+// workspace.  One tile per workgroup, ALWAYS cooperative (only instantiated with COOP): the four waves take the tile, walk
+// interleaved pairs and meet in coop_merge; there is no per-wave exit, every return in front of the barrier is
+// workgroup-uniform.  Grid: x = ((part * tiles + tile_rev) * num_seqs + seq) * num_kv_heads + kvh, tiles = ceil(max_q_len / R)
+// from the host (Params::groups), tile_rev from the sequence's last tile; workspace and merge launch are the SPLIT form's.
+// On a sequence with q_len <= R the tile is the cooperative form's (same last_pos, pairs per wave and merge; an MFMA column
+// depends on its own operand column only): bit-identical results.
+template <int D, bool SPLIT = false, bool COOP = false, bool PACK = false>
 __global__ void __launch_bounds__(WAVES * 64) pa_prefill_kernel(const Params p) {
+  static_assert(COOP || !PACK, "the head-packed form is cooperative by construction");
   constexpr int KC = D / 32;    // 32-dim chunks of a K block: one MFMA each
   constexpr int VT = D / 16;    // 16-dim tiles of the output: one MFMA each
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int items = p.num_seqs * p.num_heads;
+  const int nh = PACK ? p.num_heads >> p.g_shift : p.num_heads;   // x's innermost axis: query heads, or — packed — KV heads
+  const int items = p.num_seqs * nh;
   const int slot = blockIdx.x / items;
   const int rem = blockIdx.x - slot * items;
-  const int seq = rem / p.num_heads, head = rem - seq * p.num_heads;
+  const int seq = rem / nh, hx = rem - seq * nh;
   const int part = SPLIT ? slot / p.groups : 0;      // my context partition: tokens part * part_tokens .. + part_tokens - 1
   const int grev = SPLIT ? slot - part * p.groups : slot;
   int row_lo, q_len, L;
   if (!seq_span(p, seq, row_lo, q_len, L)) return;
   const int ctx = L - q_len;    // cached positions in front of the chunk
-  const int ngroups = (q_len + ROWS - 1) / ROWS;
+  const int ngroups = PACK ? (q_len + (TILE >> p.g_shift) - 1) >> (4 - p.g_shift) : (q_len + ROWS - 1) / ROWS;   // packed: R-row tiles
   if (grev >= ngroups) return;
-  int j0 = ((ngroups - 1 - grev) * WAVES + wave) * TILE;         // first row of my tile within the chunk
-  bool coop = false;                                              // (workgroup-uniform)
-  if constexpr (COOP) {
+  int j0 = PACK ? (ngroups - 1 - grev) << (4 - p.g_shift)
+                : ((ngroups - 1 - grev) * WAVES + wave) * TILE;   // first row of my tile within the chunk
+  bool coop = PACK;                                               // (workgroup-uniform)
+  if constexpr (COOP && !PACK) {
     coop = q_len - (ngroups - 1 - grev) * ROWS <= TILE;           // my group's live rows fit one tile: all four waves take it
     if (coop) j0 = (ngroups - 1 - grev) * ROWS;
   }
   if (!coop && j0 >= q_len) return;                               // (wave-uniform; never taken by a cooperating workgroup)
 
   const int n = lane & 15, kg = lane >> 4;
-  const int jr = min(j0 + n, q_len - 1);                 // rows past the chunk repeat its last row and are not stored
+  const int r = PACK ? n >> p.g_shift : n;               // my column's row within the tile, and its query head
+  const int head = PACK ? (hx << p.g_shift) + (n & ((1 << p.g_shift) - 1)) : hx;
+  const int jr = min(j0 + r, q_len - 1);                 // rows past the chunk repeat its last row and are not stored
   const int pos = ctx + jr;                              // my column's position: it attends to tokens 0..pos
-  const int last_pos = ctx + min(j0 + TILE - 1, q_len - 1);
+  const int last_pos = ctx + min(j0 + (PACK ? TILE >> p.g_shift : TILE) - 1, q_len - 1);
   const int nblk = last_pos / BS + 1, npair = (nblk + 1) >> 1;
   // the trips I walk: all of them, or my partition's (it starts on a pair boundary; a tile that ends below it leaves)
   int pp0 = 0, pp1 = npair;
@@ -208,7 +228,7 @@ __global__ void __launch_bounds__(WAVES * 64) pa_prefill_kernel(const Params p) 
 #pragma unroll
   for (int c = 0; c < KC; ++c) qB[c] = *reinterpret_cast<const h16x8*>(qp + 32 * c);
 
-  const int64_t head_off = (int64_t)(head / p.q_per_kv) * p.kv_head_stride;
+  const int64_t head_off = (int64_t)(PACK ? hx : head / p.q_per_kv) * p.kv_head_stride;
   const h16* kbase = p.kc + head_off + 8 * lane;
   const h16* vbase = p.vc + head_off + n * BS + 4 * kg;
   const int32_t* bt = p.block_tables + (int64_t)seq * p.max_blocks_per_seq;
@@ -324,13 +344,13 @@ __global__ void __launch_bounds__(WAVES * 64) pa_prefill_kernel(const Params p) 
   }
   if constexpr (SPLIT) {
     // unnormalised partials of the columns that see a token of this partition (the others hold sum 0 and are never merged)
-    if (j0 + n < q_len && pos >= part * p.part_tokens)
-      store_partial<D>(p.ws, p.num_tokens, p.num_heads, p.num_parts, part, row_lo + j0 + n, head, kg, o, m, lsum);
+    if (j0 + r < q_len && pos >= part * p.part_tokens)
+      store_partial<D>(p.ws, p.num_tokens, p.num_heads, p.num_parts, part, row_lo + j0 + r, head, kg, o, m, lsum);
     return;
   }
-  if (j0 + n < q_len) {
+  if (j0 + r < q_len) {
     const float inv = 1.f / lsum;   // (a stored row attends at least to token 0 and its maximum contributes exp2(0): lsum >= 1)
-    h16* op = p.out + ((int64_t)(row_lo + j0 + n) * p.num_heads + head) * D + 4 * kg;
+    h16* op = p.out + ((int64_t)(row_lo + j0 + r) * p.num_heads + head) * D + 4 * kg;
 #pragma unroll
     for (int t = 0; t < VT; ++t) {
       const h16x4 h = {(h16)(o[t][0] * inv), (h16)(o[t][1] * inv), (h16)(o[t][2] * inv), (h16)(o[t][3] * inv)};

@@ -533,6 +533,57 @@ def prefill_cooperative_for(max_q_len: int, max_seq_len: Optional[int], num_seqs
         den * int(num_seqs) * int(num_heads) <= num * int(num_cus)
 
 
+def prefill_gqa_plan(num_tokens: int, num_heads: int, head_size: int, num_seqs: int, max_q_len: int, max_seq_len: int,
+                     num_kv_heads: int, num_cus: int = 0, partition_tokens: int = 0) -> tuple:
+    """prefill_split_plan for the head-packed launch: the same rule and workspace bytes, counted on the packed grid of
+    ceil(max_q_len / (16 / G)) * num_seqs * num_kv_heads workgroups, G = num_heads / num_kv_heads."""
+    import ctypes
+
+    pt, parts, nbytes = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int64()
+    rc = _lib.load().vmi_paged_attention_prefill_gqa_plan(int(num_tokens), int(num_heads), int(head_size), int(num_seqs),
+                                                          int(max_q_len), int(max_seq_len), int(num_cus), int(partition_tokens),
+                                                          ctypes.byref(pt), ctypes.byref(parts), ctypes.byref(nbytes),
+                                                          int(num_kv_heads))
+    if rc != 0:
+        _raise_native(rc)
+    return pt.value, parts.value, nbytes.value
+
+
+PREFILL_PACK_RATIOS = (2, 4, 8, 16)
+
+
+def _pack_ratio(num_heads: int, num_kv_heads: int) -> int:
+    """num_heads / num_kv_heads when the head-packed form is built for it, else 0."""
+    num_heads, num_kv_heads = int(num_heads), int(num_kv_heads)
+    g = num_heads // num_kv_heads if num_kv_heads > 0 and num_heads % num_kv_heads == 0 else 0
+    return g if g in PREFILL_PACK_RATIOS else 0
+
+
+# pack_heads=None, read off profiles/prefill_gqa.md (MI355X, 256 CUs; 32/8 and 64/8 heads x 128, both page formats).  Chunks of
+# at most this many rows leave columns of a one-head tile empty, and the packed launch won in every such cell measured, from
+# 8 to 4 096 workgroups a partition ...
+PREFILL_PACK_MAX_ROWS = 4
+# ... while a 16-row chunk fills a one-head tile: no trip is saved, and the packed launch won only where its grid of
+# tiles * num_seqs * num_kv_heads workgroups was at most one per CU (128 and 256 workgroups; at 2 048 and 4 096 it lost).
+# Chunks of 5 - 15 rows on fuller grids, and longer chunks, were not measured: they stay with the other launches.
+PREFILL_PACK_MAX_ROWS_UNDERFILLED = 16
+
+
+def prefill_pack_heads_for(max_q_len: int, num_heads: int, num_kv_heads: int, max_seq_len: Optional[int] = None,
+                           num_seqs: int = 0, num_cus: int = 0) -> bool:
+    """What paged_attention_prefill(pack_heads=None) resolves to, from host-known bounds alone: the head-packed launch when the
+    ratio is one it is built for, max_seq_len is given (every measured launch had it), and the chunks are at most
+    PREFILL_PACK_MAX_ROWS rows — or at most PREFILL_PACK_MAX_ROWS_UNDERFILLED with no more than one packed workgroup per CU.
+    Measurements: profiles/prefill_gqa.md."""
+    g, q = _pack_ratio(num_heads, num_kv_heads), int(max_q_len)
+    if not g or max_seq_len is None or q <= 0:
+        return False
+    if q <= PREFILL_PACK_MAX_ROWS:
+        return True
+    tiles = -(-q * g // 16)
+    return q <= PREFILL_PACK_MAX_ROWS_UNDERFILLED and 0 < tiles * int(num_seqs) * int(num_kv_heads) <= int(num_cus)
+
+
 def paged_attention_prefill(
     out: torch.Tensor,
     query: torch.Tensor,
@@ -550,6 +601,7 @@ def paged_attention_prefill(
     max_seq_len: Optional[int] = None,
     partition_tokens: Optional[int] = None,
     cooperative: Optional[bool] = False,
+    pack_heads: Optional[bool] = False,
 ) -> None:
     """Tiled causal attention of a chunk of query rows per sequence over the paged cache (extension: the reference runs its
     prefill as eager masked attention, gpt2.py:46-58); writes `out` in place, returns None.
@@ -573,9 +625,18 @@ def paged_attention_prefill(
     look-ahead rows, a chunk's tail, a 16-row chunk) the workgroup's four waves share the one tile's context and merge in LDS,
     where the plain form leaves three of them idle; groups with more live rows compute bit for bit what the plain form does.
     False (default): the plain launches.  True: the cooperative ones, split or not as above (without max_seq_len the block
-    table's capacity stands in as the bound).  None: the measured rule, prefill_cooperative_for — never without max_seq_len."""
+    table's capacity stands in as the bound).  None: the measured rule, prefill_cooperative_for — never without max_seq_len.
+
+    `pack_heads` picks the HEAD-PACKED form for grouped-query attention (num_heads / num_kv_heads in 2, 4, 8, 16; any other
+    ratio raises): a tile's 16 columns are (row, query head of one KV head) pairs, so a short chunk — a decode row, look-ahead
+    rows — walks its context once per KV head with full tiles, where the other forms walk it once per query head.  False
+    (default): the launches above.  True: the packed ones, split or not by max_seq_len / partition_tokens through
+    prefill_gqa_plan (without max_seq_len the block table's capacity stands in as the bound); `cooperative` is not consulted,
+    the form is cooperative by construction.  None: the measured rule, prefill_pack_heads_for — never without max_seq_len."""
     if cooperative is not None and not isinstance(cooperative, bool):
         raise RuntimeError(f"paged_attention_prefill: cooperative must be True, False or None, got {cooperative!r}")
+    if pack_heads is not None and not isinstance(pack_heads, bool):
+        raise RuntimeError(f"paged_attention_prefill: pack_heads must be True, False or None, got {pack_heads!r}")
     if max_seq_len is None and partition_tokens is not None:
         raise RuntimeError("paged_attention_prefill: partition_tokens needs max_seq_len (the host-known bound on seq_lens)")
     fp8 = _check_kv_cache_dtype(kv_cache_dtype)     # first: an unknown or unbuilt dtype is reported whatever the tensors are
@@ -646,24 +707,35 @@ def paged_attention_prefill(
             block_tables.data_ptr(), seq_lens.data_ptr(), cu_q_lens.data_ptr(),
             num_seqs, int(max_q_len), block_size, ts[1], qst[0], kst[0], kst[1], index, _stream_of(index))
     lib = _lib.load()
+    pack = pack_heads
+    if pack is None:
+        pack = prefill_pack_heads_for(max_q_len, num_heads, num_kv_heads, max_seq_len, num_seqs, _num_cus(index))
+    if pack and not _pack_ratio(num_heads, num_kv_heads):
+        raise RuntimeError(f"paged_attention_prefill: pack_heads is built for num_heads / num_kv_heads in {PREFILL_PACK_RATIOS}, "
+                           f"got num_heads={num_heads} num_kv_heads={num_kv_heads}")
     coop = cooperative
-    if coop is None:
+    if coop is None and not pack:
         coop = max_seq_len is not None and prefill_cooperative_for(max_q_len, max_seq_len, num_seqs, num_heads, _num_cus(index))
-    if coop and max_seq_len is None:                    # one cooperative launch, bounded by what the block table can hold
+    if (coop or pack) and max_seq_len is None:          # one cooperative launch, bounded by what the block table can hold
         bound = min(16 * ts[1], 2 ** 31 - 32)
         tail = (bound, max(32, (bound + 31) // 32 * 32), None, 0)
-        rc = lib.vmi_paged_attention_prefill_coop_fp8(*args, *tail, float(kv_scale)) if fp8 else \
-            lib.vmi_paged_attention_prefill_coop_f16(*args, *tail)
+        form = "gqa" if pack else "coop"
+        rc = getattr(lib, f"vmi_paged_attention_prefill_{form}_fp8")(*args, *tail, float(kv_scale)) if fp8 else \
+            getattr(lib, f"vmi_paged_attention_prefill_{form}_f16")(*args, *tail)
     elif max_seq_len is not None:
-        pt, parts, nbytes = prefill_split_plan(num_tokens, num_heads, head_size, num_seqs, max_q_len, max_seq_len,
-                                               _num_cus(index), int(partition_tokens or 0))
+        if pack:
+            pt, parts, nbytes = prefill_gqa_plan(num_tokens, num_heads, head_size, num_seqs, max_q_len, max_seq_len,
+                                                 num_kv_heads, _num_cus(index), int(partition_tokens or 0))
+        else:
+            pt, parts, nbytes = prefill_split_plan(num_tokens, num_heads, head_size, num_seqs, max_q_len, max_seq_len,
+                                                   _num_cus(index), int(partition_tokens or 0))
         ws = prefill_workspace_for(index, nbytes, args[-1]) if parts > 1 else None
         if ws is None:                                  # one partition (or capturing without a workspace): the single launch
             pt, ws_ptr, ws_len = max(32, (int(max_seq_len) + 31) // 32 * 32), None, 0
         else:
             ws_ptr, ws_len = ws.data_ptr(), ws.numel()
         tail = (int(max_seq_len), pt, ws_ptr, ws_len)
-        form = "coop" if coop else "split"
+        form = "gqa" if pack else "coop" if coop else "split"
         rc = getattr(lib, f"vmi_paged_attention_prefill_{form}_fp8")(*args, *tail, float(kv_scale)) if fp8 else \
             getattr(lib, f"vmi_paged_attention_prefill_{form}_f16")(*args, *tail)
     elif fp8:
