@@ -547,6 +547,45 @@ int vmi_paged_attention_prefill_gqa_plan(
     int64_t* workspace_bytes, int32_t num_kv_heads);
 
 /*
+ * The same operator with a SHARED PROMPT PREFIX attended once per batch (cascade attention; added under ABI 22 like the entries
+ * above): for a batch whose sequences all begin with the same system prompt or few-shot header, where the forms above walk
+ * those pages once per (sequence, head).  Three launches on `stream`: (1) prefix tiles — a tile is 16 consecutive rows of the
+ * PACKED query array for one head, across sequence boundaries, and walks ONE copy of the prefix, its four waves on interleaved
+ * pairs of blocks, merged in LDS — write the partials of partition 0; (2) the partition kernels of `suffix_form`, their grid
+ * starting at partition 1, write every sequence's own suffix; (3) the merge launch of vmi_paged_attention_prefill_split_*,
+ * unchanged.  Fixed orders, no atomics: run-to-run bit-identical.  Kernels: pa_prefill_prefix_kernel / pa_prefill_prefix_fp8_kernel
+ * (the PREFIX form in vllmini_amd/csrc/pa_prefill.hpp / pa_prefill_fp8.hpp).
+ * Arguments and validation are vmi_paged_attention_prefill_split_f16's / _fp8's, and in addition:
+ *   shared_prefix_len  P, a positive multiple of 32 and less than max_seq_len (else VMI_E_SHAPE).  CONTRACT: the first P cached
+ *                      positions of every sequence of the call are the same tokens in the same blocks, and the block indices of
+ *                      positions 0 .. P-1 are read from ROW 0 of block_tables only — the first P / 16 entries of every other row
+ *                      are never read.  A row whose position lies inside the prefix (a sequence with fewer than P tokens in front
+ *                      of its chunk) is masked by selection, as everywhere.
+ *   partition_tokens   must equal shared_prefix_len (the prefix IS partition 0), else VMI_E_SHAPE; the workspace is the split
+ *                      plan's for that partition size, vmi_paged_attention_prefill_split_plan(..., partition_tokens_in = P).
+ *   suffix_form        0: the plain partition kernels, 1: the cooperative ones, 2: the head-packed ones (num_heads / num_kv_heads
+ *                      in {2, 4, 8, 16}, else VMI_E_KV_HEADS); anything else VMI_E_SHAPE.
+ * Results are those of the unshared entries on tables that all name the shared blocks (same accuracy bound).  The prefix tiles
+ * take one query head each; packing the heads of a KV head into them is not built.
+ */
+int vmi_paged_attention_prefill_prefix_f16(
+    void* out, const void* query, const void* key_cache, const void* value_cache,
+    int32_t num_tokens, int32_t num_heads, int32_t head_size, int32_t num_kv_heads, float scale,
+    const int32_t* block_tables, const int32_t* seq_lens, const int32_t* cu_q_lens,
+    int32_t num_seqs, int32_t max_q_len, int32_t block_size, int32_t max_num_blocks_per_seq,
+    int64_t q_stride, int64_t kv_block_stride, int64_t kv_head_stride, int32_t device, void* stream,
+    int32_t max_seq_len, int32_t partition_tokens, void* workspace, int64_t workspace_bytes,
+    int32_t shared_prefix_len, int32_t suffix_form);
+int vmi_paged_attention_prefill_prefix_fp8(
+    void* out, const void* query, const void* key_cache, const void* value_cache,
+    int32_t num_tokens, int32_t num_heads, int32_t head_size, int32_t num_kv_heads, float scale,
+    const int32_t* block_tables, const int32_t* seq_lens, const int32_t* cu_q_lens,
+    int32_t num_seqs, int32_t max_q_len, int32_t block_size, int32_t max_num_blocks_per_seq,
+    int64_t q_stride, int64_t kv_block_stride, int64_t kv_head_stride, int32_t device, void* stream,
+    int32_t max_seq_len, int32_t partition_tokens, void* workspace, int64_t workspace_bytes, float kv_scale,
+    int32_t shared_prefix_len, int32_t suffix_form);
+
+/*
  * The pool's preemption move (extension; counterpart of BlockManager.swap_to_cpu / swap_from_cpu,
  * vllmini/block_manager.py:70-87, which the reference runs as one copy per block, cache_kernels.cu:56-62): ONE launch on
  * `stream` moves block_mapping[i] = (src block, dst block) of BOTH caches for every i.

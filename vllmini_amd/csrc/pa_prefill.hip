@@ -103,6 +103,19 @@ static void launch_packed(const prefill::ParamsFp8& p, int head_size, dim3 grid,
   else
     hipLaunchKernelGGL((prefill::pa_prefill_fp8_kernel<128, SPLIT, true, true>), grid, block, 0, st, p);
 }
+// the shared-prefix tiles (PREFIX): partition 0 of every row of the packed batch, one tile of 16 rows x one head per workgroup
+static void launch_prefix(const prefill::Params& p, int head_size, dim3 grid, dim3 block, hipStream_t st) {
+  if (head_size == 64)
+    hipLaunchKernelGGL(prefill::pa_prefill_prefix_kernel<64>, grid, block, 0, st, p);
+  else
+    hipLaunchKernelGGL(prefill::pa_prefill_prefix_kernel<128>, grid, block, 0, st, p);
+}
+static void launch_prefix(const prefill::ParamsFp8& p, int head_size, dim3 grid, dim3 block, hipStream_t st) {
+  if (head_size == 64)
+    hipLaunchKernelGGL(prefill::pa_prefill_prefix_fp8_kernel<64>, grid, block, 0, st, p);
+  else
+    hipLaunchKernelGGL(prefill::pa_prefill_prefix_fp8_kernel<128>, grid, block, 0, st, p);
+}
 template <bool SPLIT, class P>
 static void launch_tiles(const P& p, int head_size, bool coop, dim3 grid, dim3 block, hipStream_t st) {
   if (p.g_shift >= 0)
@@ -116,6 +129,9 @@ static void launch_tiles(const P& p, int head_size, bool coop, dim3 grid, dim3 b
 // max_seq_len < 0: the plain entries — never split, no bound on seq_lens.  coop: the cooperative form of the tile kernels
 // (pa_prefill.hpp, COOP) — same grid, same Params, same merge launch.  pack: the head-packed form (PACK) — one tile of
 // 16 / G rows x G heads per workgroup, a grid over KV heads; Params, workspace and merge launch are the same again.
+// prefix > 0 (the shared-prefix entries, which checked it: a multiple of 32, == partition_tokens, < max_seq_len — so there are
+// at least two partitions and a workspace): partition 0 comes from the PREFIX tiles, launched first; coop / pack then are the
+// form of the SUFFIX launch, whose partition axis starts at part0 = 1; the merge launch is the same.
 static int launch_pa_prefill(void* out, const void* query, const void* key_cache, const void* value_cache,
                              int32_t num_tokens, int32_t num_heads, int32_t head_size, int32_t num_kv_heads, float scale,
                              const int32_t* block_tables, const int32_t* seq_lens, const int32_t* cu_q_lens,
@@ -123,7 +139,7 @@ static int launch_pa_prefill(void* out, const void* query, const void* key_cache
                              int64_t q_stride, int64_t kv_block_stride, int64_t kv_head_stride, int32_t device,
                              void* stream, bool fp8, float kv_scale, int32_t max_seq_len = -1,
                              int32_t partition_tokens = 0, void* workspace = nullptr, int64_t workspace_bytes = 0,
-                             bool coop = false, bool pack = false) {
+                             bool coop = false, bool pack = false, int32_t prefix = 0) {
   // one validation for both page formats; the cache strides are in cache elements: halves, or bytes when fp8
   const bool empty = num_tokens == 0 || num_seqs == 0;   // (torch hands out null data pointers for empty tensors)
   if (!key_cache || !value_cache || (!empty && (!out || !query || !block_tables || !seq_lens || !cu_q_lens)))
@@ -168,9 +184,10 @@ static int launch_pa_prefill(void* out, const void* query, const void* key_cache
   if (empty || max_q_len == 0 || max_seq_len == 0) return VMI_OK;
   const int64_t tile_rows = pack ? prefill::TILE >> g_shift : prefill::ROWS;   // chunk rows per workgroup
   const int64_t groups = ((int64_t)max_q_len + tile_rows - 1) / tile_rows;
-  const int64_t wgs = groups * num_seqs * (pack ? num_kv_heads : num_heads) * parts;
+  const int64_t wgs = groups * num_seqs * (pack ? num_kv_heads : num_heads) * (parts - (prefix > 0));
+  const int64_t prefix_wgs = ((int64_t)num_tokens + prefill::TILE - 1) / prefill::TILE * num_heads;
   constexpr int MERGE_ROWS = 1024 / 128;                  // the merge's rows per workgroup at its smallest (D 128)
-  if ((int64_t)num_seqs * num_heads >= (1ll << 31) || wgs >= (1ll << 31) ||
+  if ((int64_t)num_seqs * num_heads >= (1ll << 31) || wgs >= (1ll << 31) || (prefix > 0 && prefix_wgs >= (1ll << 31)) ||
       (parts > 1 && ((int64_t)max_q_len + MERGE_ROWS - 1) / MERGE_ROWS * num_seqs * num_heads >= (1ll << 31)))
     return fail(VMI_E_SHAPE, "paged_attention_prefill: %lld workgroups exceed the grid", (long long)wgs);
 
@@ -196,12 +213,20 @@ static int launch_pa_prefill(void* out, const void* query, const void* key_cache
     p.num_parts = parts;
     p.groups = (int32_t)groups;
     p.g_shift = g_shift;
+    p.part0 = 0;
   };
 
   DeviceGuard guard(device);
   if (guard.err != hipSuccess) return hip_fail(guard.err, "paged_attention_prefill: hipSetDevice");
   const dim3 grid((unsigned)wgs), block(prefill::WAVES * 64);
   hipStream_t st = static_cast<hipStream_t>(stream);
+  // the shared-prefix tiles in front of the suffix launch, which then starts at partition 1
+  auto prefix_tiles = [&](auto& p) -> hipError_t {
+    if (prefix <= 0) return hipSuccess;
+    launch_prefix(p, head_size, dim3((unsigned)prefix_wgs), block, st);
+    p.part0 = 1;
+    return hipGetLastError();
+  };
   if (parts > 1) {
     // partition kernels, then the merge, on the caller's stream: the second launch is the only synchronisation
     prefill::MergeParams mp;
@@ -222,11 +247,13 @@ static int launch_pa_prefill(void* out, const void* query, const void* key_cache
       fill(p);
       p.scale_log2e = (scale * kv_scale) * 1.4426950408889634f;
       p.kv_scale = kv_scale;
+      if (const hipError_t pe = prefix_tiles(p)) return hip_fail(pe, "paged_attention_prefill shared-prefix launch");
       launch_tiles<true>(p, head_size, coop, grid, block, st);
     } else {
       prefill::Params p;
       fill(p);
       p.scale_log2e = scale * 1.4426950408889634f;
+      if (const hipError_t pe = prefix_tiles(p)) return hip_fail(pe, "paged_attention_prefill shared-prefix launch");
       launch_tiles<true>(p, head_size, coop, grid, block, st);
     }
     hipError_t e = hipGetLastError();
@@ -402,4 +429,56 @@ extern "C" int vmi_paged_attention_prefill_gqa_fp8(
                                 block_tables, seq_lens, cu_q_lens, num_seqs, max_q_len, block_size, max_num_blocks_per_seq,
                                 q_stride, kv_block_stride, kv_head_stride, device, stream, true, kv_scale, max_seq_len,
                                 partition_tokens, workspace, workspace_bytes, true, true);
+}
+
+// the shared-prefix entries' own checks, in front of the common ones; -> VMI_OK and the suffix launch's form
+static int check_prefix(int32_t max_seq_len, int32_t partition_tokens, int32_t shared_prefix_len, int32_t suffix_form) {
+  if (max_seq_len < 0) return vmi::fail(VMI_E_SHAPE, "paged_attention_prefill: negative max_seq_len=%d", max_seq_len);
+  if (shared_prefix_len <= 0 || (shared_prefix_len & 31))
+    return vmi::fail(VMI_E_SHAPE, "paged_attention_prefill: shared_prefix_len must be a positive multiple of 32, got %d",
+                     shared_prefix_len);
+  if (shared_prefix_len >= max_seq_len)
+    return vmi::fail(VMI_E_SHAPE, "paged_attention_prefill: shared_prefix_len=%d must be less than max_seq_len=%d",
+                     shared_prefix_len, max_seq_len);
+  if (partition_tokens != shared_prefix_len)
+    return vmi::fail(VMI_E_SHAPE, "paged_attention_prefill: partition_tokens=%d must equal shared_prefix_len=%d (the prefix is "
+                     "partition 0)", partition_tokens, shared_prefix_len);
+  if (suffix_form < 0 || suffix_form > 2)
+    return vmi::fail(VMI_E_SHAPE, "paged_attention_prefill: suffix_form must be 0 (plain), 1 (cooperative) or 2 (head-packed), "
+                     "got %d", suffix_form);
+  return VMI_OK;
+}
+
+extern "C" int vmi_paged_attention_prefill_prefix_f16(
+    void* out, const void* query, const void* key_cache, const void* value_cache,
+    int32_t num_tokens, int32_t num_heads, int32_t head_size, int32_t num_kv_heads, float scale,
+    const int32_t* block_tables, const int32_t* seq_lens, const int32_t* cu_q_lens,
+    int32_t num_seqs, int32_t max_q_len, int32_t block_size, int32_t max_num_blocks_per_seq,
+    int64_t q_stride, int64_t kv_block_stride, int64_t kv_head_stride, int32_t device, void* stream,
+    int32_t max_seq_len, int32_t partition_tokens, void* workspace, int64_t workspace_bytes,
+    int32_t shared_prefix_len, int32_t suffix_form) {
+  const int rc = check_prefix(max_seq_len, partition_tokens, shared_prefix_len, suffix_form);
+  if (rc != VMI_OK) return rc;
+  return vmi::launch_pa_prefill(out, query, key_cache, value_cache, num_tokens, num_heads, head_size, num_kv_heads, scale,
+                                block_tables, seq_lens, cu_q_lens, num_seqs, max_q_len, block_size, max_num_blocks_per_seq,
+                                q_stride, kv_block_stride, kv_head_stride, device, stream, false, 1.0f, max_seq_len,
+                                partition_tokens, workspace, workspace_bytes, suffix_form >= 1, suffix_form == 2,
+                                shared_prefix_len);
+}
+
+extern "C" int vmi_paged_attention_prefill_prefix_fp8(
+    void* out, const void* query, const void* key_cache, const void* value_cache,
+    int32_t num_tokens, int32_t num_heads, int32_t head_size, int32_t num_kv_heads, float scale,
+    const int32_t* block_tables, const int32_t* seq_lens, const int32_t* cu_q_lens,
+    int32_t num_seqs, int32_t max_q_len, int32_t block_size, int32_t max_num_blocks_per_seq,
+    int64_t q_stride, int64_t kv_block_stride, int64_t kv_head_stride, int32_t device, void* stream,
+    int32_t max_seq_len, int32_t partition_tokens, void* workspace, int64_t workspace_bytes, float kv_scale,
+    int32_t shared_prefix_len, int32_t suffix_form) {
+  const int rc = check_prefix(max_seq_len, partition_tokens, shared_prefix_len, suffix_form);
+  if (rc != VMI_OK) return rc;
+  return vmi::launch_pa_prefill(out, query, key_cache, value_cache, num_tokens, num_heads, head_size, num_kv_heads, scale,
+                                block_tables, seq_lens, cu_q_lens, num_seqs, max_q_len, block_size, max_num_blocks_per_seq,
+                                q_stride, kv_block_stride, kv_head_stride, device, stream, true, kv_scale, max_seq_len,
+                                partition_tokens, workspace, workspace_bytes, suffix_form >= 1, suffix_form == 2,
+                                shared_prefix_len);
 }

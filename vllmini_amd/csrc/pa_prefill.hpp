@@ -68,6 +68,8 @@ struct Params {
   int32_t part_tokens, num_parts, groups;   // tokens per context partition (a multiple of 32), partitions, the host's bound on 64-row groups
   // the head-packed form only (PACK, see below), where `groups` is the host's bound on R-row tiles
   int32_t g_shift;              // log2 G, G = q_per_kv in {2, 4, 8, 16}
+  // the suffix launch behind the shared-prefix tiles only (PREFIX, see below); 0 in every other launch
+  int32_t part0;                // the grid's first partition: its partition axis counts num_parts - part0 from here
 };
 
 // THE guard of every kernel of the operator (unsplit, partition form, merge): a sequence with nothing to do, or with
@@ -144,6 +146,104 @@ __device__ __forceinline__ bool coop_merge(CoopLds<D>& lds, int wave, int lane, 
   return true;
 }
 
+// What lane (n, kg) knows about ITS query column before the walk, in every form and over both page formats; the forms differ in
+// how blockIdx.x and n become one of these (chunk_column, prefix_column), not in the trip behind it.
+struct Column {
+  int part;          // my context partition (0 unless SPLIT)
+  int head, kv_head; // the column's query head and the KV head whose pages the tile walks
+  int table_row;     // the block_tables row the walk reads
+  int q_row;         // the column's row of `query` (a dead column repeats a live one)
+  int row0, live_rows;  // chunk forms: the tile's first row of `out` / the workspace (column n: + its row r within the tile), and
+                     // how many of the tile's rows are stored — wave-uniform both, so nothing per lane waits through the walk
+  int out_row;       // PREFIX: the column's row of `out` / the workspace ...
+  int pos;           // the column attends to tokens 0 .. pos
+  int last_pos;      // the tile's last visible position: bounds the walk, and V is cleared past it
+  bool live;         // ... and whether it is stored
+  bool coop;         // the workgroup's four waves share this tile (workgroup-uniform)
+  bool select;       // PREFIX only — false: no column of the tile needs the causal select
+};
+
+// The column map of the chunk forms (plain, SPLIT, COOP, PACK: the kernels' comment below).  -> false: leave.  A return here is
+// wave-uniform, and workgroup-uniform but for `j0 >= q_len`, which a cooperating workgroup never takes.
+template <bool SPLIT, bool COOP, bool PACK, class P>
+__device__ __forceinline__ bool chunk_column(const P& p, int wave, int n, Column& c) {
+  const int nh = PACK ? p.num_heads >> p.g_shift : p.num_heads;   // x's innermost axis: query heads, or — packed — KV heads
+  const int items = p.num_seqs * nh;
+  const int slot = blockIdx.x / items;
+  const int rem = blockIdx.x - slot * items;
+  const int seq = rem / nh, hx = rem - seq * nh;
+  const int pslot = SPLIT ? slot / p.groups : 0;
+  c.part = pslot + (SPLIT ? p.part0 : 0);              // my context partition: tokens part * part_tokens .. + part_tokens - 1
+  const int grev = SPLIT ? slot - pslot * p.groups : slot;
+  int row_lo, q_len, L;
+  if (!seq_span(p, seq, row_lo, q_len, L)) return false;
+  const int ctx = L - q_len;    // cached positions in front of the chunk
+  const int ngroups = PACK ? (q_len + (TILE >> p.g_shift) - 1) >> (4 - p.g_shift) : (q_len + ROWS - 1) / ROWS;   // packed: R-row tiles
+  if (grev >= ngroups) return false;
+  int j0 = PACK ? (ngroups - 1 - grev) << (4 - p.g_shift)
+                : ((ngroups - 1 - grev) * WAVES + wave) * TILE;   // first row of my tile within the chunk
+  c.coop = PACK;                                                  // (workgroup-uniform)
+  if constexpr (COOP && !PACK) {
+    c.coop = q_len - (ngroups - 1 - grev) * ROWS <= TILE;         // my group's live rows fit one tile: all four waves take it
+    if (c.coop) j0 = (ngroups - 1 - grev) * ROWS;
+  }
+  if (!c.coop && j0 >= q_len) return false;                       // (wave-uniform; never taken by a cooperating workgroup)
+
+  const int r = PACK ? n >> p.g_shift : n;               // my column's row within the tile, and its query head
+  c.head = PACK ? (hx << p.g_shift) + (n & ((1 << p.g_shift) - 1)) : hx;
+  c.kv_head = PACK ? hx : c.head / p.q_per_kv;
+  c.table_row = seq;
+  const int jr = min(j0 + r, q_len - 1);                 // rows past the chunk repeat its last row and are not stored
+  c.q_row = row_lo + jr;
+  c.row0 = row_lo + j0;
+  c.live_rows = q_len - j0;
+  c.pos = ctx + jr;                                      // my column's position: it attends to tokens 0..pos
+  c.last_pos = ctx + min(j0 + (PACK ? TILE >> p.g_shift : TILE) - 1, q_len - 1);
+  c.select = true;
+  return true;
+}
+
+// The column map of the PREFIX form (the kernels' comment below): column n of tile blockIdx.x / num_heads is row t = 16 * tile + n
+// of the PACKED query array, whatever sequence owns it.  The lane finds that sequence by binary search in cu_q_lens (the last s
+// with cu_q_lens[s] <= t; every index it reads is inside the array, whatever the array holds), takes the guard's word on it,
+// and gets pos = seq_lens[s] - q_len + (t - row_lo).  A column past num_tokens, of a sequence the guard rejects, or that the
+// sequence found does not own is DEAD: it repeats row min(t, num_tokens - 1) of `query` at the tile's largest position and is
+// not stored.  last_pos = min(largest live pos, P - 1), P = part_tokens; select = some live column ends inside the prefix.
+// The four waves of the workgroup map the same sixteen columns, so the reductions over them — and the return on a tile
+// with no live column — are workgroup-uniform.
+template <class P>
+__device__ __forceinline__ bool prefix_column(const P& p, int n, Column& c) {
+  const int tile = blockIdx.x / p.num_heads;
+  c.head = blockIdx.x - tile * p.num_heads;
+  c.kv_head = c.head / p.q_per_kv;
+  c.part = 0;
+  c.table_row = 0;                                       // the prefix's blocks are read from row 0 of block_tables ONLY
+  c.coop = true;
+  c.out_row = tile * TILE + n;
+  c.q_row = min(c.out_row, p.num_tokens - 1);
+  int s = 0, hi = p.num_seqs - 1;
+  while (s < hi) {
+    const int mid = (s + hi + 1) >> 1;
+    if (p.cu_q_lens[mid] <= c.q_row) s = mid; else hi = mid - 1;
+  }
+  int row_lo, q_len, L;
+  c.live = seq_span(p, s, row_lo, q_len, L) && c.out_row >= row_lo && c.out_row < row_lo + q_len;
+  c.pos = c.live ? L - q_len + (c.out_row - row_lo) : -1;
+  int pos_hi = c.pos, pos_lo = c.live ? c.pos : 0x7fffffff;
+#pragma unroll
+  for (int d = 1; d < TILE; d <<= 1) {                   // over the sixteen columns (the four kg copies of a column agree)
+    pos_hi = max(pos_hi, __shfl_xor(pos_hi, d));
+    pos_lo = min(pos_lo, __shfl_xor(pos_lo, d));
+  }
+  pos_hi = __builtin_amdgcn_readfirstlane(pos_hi);
+  pos_lo = __builtin_amdgcn_readfirstlane(pos_lo);
+  if (pos_hi < 0) return false;
+  if (!c.live) c.pos = pos_hi;
+  c.last_pos = min(pos_hi, p.part_tokens - 1);
+  c.select = pos_lo < p.part_tokens - 1;
+  return true;
+}
+
 // Grid: one workgroup per (64-row group, sequence, head), x = group_rev * (num_seqs * num_heads) + seq * num_heads + head.
 // group_rev counts a sequence's groups from its LAST one, so the first num_seqs * num_heads workgroups of the launch are
 // every sequence's longest causal range; a sequence with fewer groups than the host bound leaves the surplus at once.
@@ -180,58 +280,57 @@ __device__ __forceinline__ bool coop_merge(CoopLds<D>& lds, int wave, int lane, 
 // from the host (Params::groups), tile_rev from the sequence's last tile; workspace and merge launch are the SPLIT form's.
 // On a sequence with q_len <= R the tile is the cooperative form's (same last_pos, pairs per wave and merge; an MFMA column
 // depends on its own operand column only): bit-identical results.
-template <int D, bool SPLIT = false, bool COOP = false, bool PACK = false>
-__global__ void __launch_bounds__(WAVES * 64) pa_prefill_kernel(const Params p) {
+//
+// PREFIX (the shared-prefix form — cascade attention — for a batch whose sequences all begin with the same P = part_tokens cached
+// tokens in the same blocks; the kernel is pa_prefill_prefix_kernel<D>, below): the forms above walk those blocks once per (sequence,
+// head).  Here the 16 columns of a tile are 16 CONSECUTIVE ROWS OF THE PACKED BATCH for one query head — a tile may span sequences
+// (prefix_column) — and the tile walks ONE copy of the prefix, read through row 0 of block_tables: partition 0 of the SPLIT scheme
+// with PT = P.  It writes that partition's partials; the chunk forms, launched with part0 = 1, write partitions 1 .. of every
+// sequence's own suffix, and the untouched merge launch folds them — three launches, one stream.  One tile per workgroup, ALWAYS
+// cooperative: wave w walks pairs w, w + 4, ... of the tile's npair <= P / 32, the four meet in coop_merge, wave 0 calls
+// store_partial(part 0), unnormalised (fp8: without kv_scale — the merge applies it).  A wave with no pair keeps m = -3e38, l = 0,
+// o = 0 and still reaches the barrier.  THE BARRIER RULE: there is one return in front of the barrier, a tile with no live column,
+// and it is workgroup-uniform because the four waves compute the same column map; the loop holds no exit.  Masking: a column that
+// ends inside the prefix (a sequence with fewer than P tokens in front of its chunk) gets -inf by selection past its pos; V is
+// cleared past the tile's LARGEST pos on the last pair, as in the other forms; when the tile's smallest pos is >= P - 1 — the
+// normal case — the select is skipped, wave-uniformly.  Grid: x = tile * num_heads + head, tiles = ceil(num_tokens / 16):
+// neighbours in x are the heads of one tile, so the heads of a KV head read the same pages at the same time.  (Packing them
+// into one tile, as PACK does, is the follow-up.)
+template <int D, bool SPLIT, bool COOP, bool PACK, bool PREFIX>
+__device__ __forceinline__ void prefill_tile(const Params& p) {
   static_assert(COOP || !PACK, "the head-packed form is cooperative by construction");
+  static_assert(!PREFIX || (SPLIT && COOP && !PACK), "the shared-prefix form is a cooperative tile of partition 0, one query head");
   constexpr int KC = D / 32;    // 32-dim chunks of a K block: one MFMA each
   constexpr int VT = D / 16;    // 16-dim tiles of the output: one MFMA each
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int nh = PACK ? p.num_heads >> p.g_shift : p.num_heads;   // x's innermost axis: query heads, or — packed — KV heads
-  const int items = p.num_seqs * nh;
-  const int slot = blockIdx.x / items;
-  const int rem = blockIdx.x - slot * items;
-  const int seq = rem / nh, hx = rem - seq * nh;
-  const int part = SPLIT ? slot / p.groups : 0;      // my context partition: tokens part * part_tokens .. + part_tokens - 1
-  const int grev = SPLIT ? slot - part * p.groups : slot;
-  int row_lo, q_len, L;
-  if (!seq_span(p, seq, row_lo, q_len, L)) return;
-  const int ctx = L - q_len;    // cached positions in front of the chunk
-  const int ngroups = PACK ? (q_len + (TILE >> p.g_shift) - 1) >> (4 - p.g_shift) : (q_len + ROWS - 1) / ROWS;   // packed: R-row tiles
-  if (grev >= ngroups) return;
-  int j0 = PACK ? (ngroups - 1 - grev) << (4 - p.g_shift)
-                : ((ngroups - 1 - grev) * WAVES + wave) * TILE;   // first row of my tile within the chunk
-  bool coop = PACK;                                               // (workgroup-uniform)
-  if constexpr (COOP && !PACK) {
-    coop = q_len - (ngroups - 1 - grev) * ROWS <= TILE;           // my group's live rows fit one tile: all four waves take it
-    if (coop) j0 = (ngroups - 1 - grev) * ROWS;
-  }
-  if (!coop && j0 >= q_len) return;                               // (wave-uniform; never taken by a cooperating workgroup)
-
   const int n = lane & 15, kg = lane >> 4;
-  const int r = PACK ? n >> p.g_shift : n;               // my column's row within the tile, and its query head
-  const int head = PACK ? (hx << p.g_shift) + (n & ((1 << p.g_shift) - 1)) : hx;
-  const int jr = min(j0 + r, q_len - 1);                 // rows past the chunk repeat its last row and are not stored
-  const int pos = ctx + jr;                              // my column's position: it attends to tokens 0..pos
-  const int last_pos = ctx + min(j0 + (PACK ? TILE >> p.g_shift : TILE) - 1, q_len - 1);
+  Column col;
+  if constexpr (PREFIX) {
+    if (!prefix_column(p, n, col)) return;                 // (workgroup-uniform)
+  } else {
+    if (!chunk_column<SPLIT, COOP, PACK>(p, wave, n, col)) return;
+  }
+  const int part = col.part, head = col.head, pos = col.pos, last_pos = col.last_pos;
+  const bool coop = col.coop;
   const int nblk = last_pos / BS + 1, npair = (nblk + 1) >> 1;
   // the trips I walk: all of them, or my partition's (it starts on a pair boundary; a tile that ends below it leaves)
   int pp0 = 0, pp1 = npair;
-  if constexpr (SPLIT) {
+  if constexpr (SPLIT && !PREFIX) {
     if (last_pos < part * p.part_tokens) return;           // (wave-uniform; workgroup-uniform when cooperating)
     pp0 = part * (p.part_tokens >> 5);
     pp1 = min(npair, pp0 + (p.part_tokens >> 5));
   }
 
-  const h16* qp = p.q + (int64_t)(row_lo + jr) * p.q_stride + (int64_t)head * D + 8 * kg;
+  const h16* qp = p.q + (int64_t)col.q_row * p.q_stride + (int64_t)head * D + 8 * kg;
   h16x8 qB[KC];
 #pragma unroll
   for (int c = 0; c < KC; ++c) qB[c] = *reinterpret_cast<const h16x8*>(qp + 32 * c);
 
-  const int64_t head_off = (int64_t)(PACK ? hx : head / p.q_per_kv) * p.kv_head_stride;
+  const int64_t head_off = (int64_t)col.kv_head * p.kv_head_stride;
   const h16* kbase = p.kc + head_off + 8 * lane;
   const h16* vbase = p.vc + head_off + n * BS + 4 * kg;
-  const int32_t* bt = p.block_tables + (int64_t)seq * p.max_blocks_per_seq;
+  const int32_t* bt = p.block_tables + (int64_t)col.table_row * p.max_blocks_per_seq;
 
   // a pair's physical blocks; the absent second block of an odd count re-reads the first (its tokens are masked)
   auto phys_of = [&](int pp, int i) -> int64_t {
@@ -286,6 +385,11 @@ __global__ void __launch_bounds__(WAVES * 64) pa_prefill_kernel(const Params p) 
 #pragma unroll
       for (int c = 0; c < KC; ++c) acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(kcur[i][c], qB[c], acc, 0, 0, 0);
       const int tok0 = (2 * pp + i) * BS + 4 * kg;
+      if (PREFIX && !col.select) {   // (wave-uniform: every column of the tile sees the whole prefix)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) mx = fmaxf(mx, s[i][r] = acc[r] * p.scale_log2e);
+        continue;
+      }
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         s[i][r] = (tok0 + r <= pos) ? acc[r] * p.scale_log2e : -INFINITY;
@@ -342,21 +446,33 @@ __global__ void __launch_bounds__(WAVES * 64) pa_prefill_kernel(const Params p) 
       if (!coop_merge<D>(lds, wave, lane, o, m, lsum)) return;
     }
   }
+  const int r = PACK ? n >> p.g_shift : n;               // my column's row within the tile
+  const bool live = PREFIX ? col.live : r < col.live_rows;
+  const int out_row = PREFIX ? col.out_row : col.row0 + r;
   if constexpr (SPLIT) {
     // unnormalised partials of the columns that see a token of this partition (the others hold sum 0 and are never merged)
-    if (j0 + r < q_len && pos >= part * p.part_tokens)
-      store_partial<D>(p.ws, p.num_tokens, p.num_heads, p.num_parts, part, row_lo + j0 + r, head, kg, o, m, lsum);
+    if (live && pos >= part * p.part_tokens)
+      store_partial<D>(p.ws, p.num_tokens, p.num_heads, p.num_parts, part, out_row, head, kg, o, m, lsum);
     return;
   }
-  if (j0 + r < q_len) {
+  if (live) {
     const float inv = 1.f / lsum;   // (a stored row attends at least to token 0 and its maximum contributes exp2(0): lsum >= 1)
-    h16* op = p.out + ((int64_t)(row_lo + j0 + r) * p.num_heads + head) * D + 4 * kg;
+    h16* op = p.out + ((int64_t)out_row * p.num_heads + head) * D + 4 * kg;
 #pragma unroll
     for (int t = 0; t < VT; ++t) {
       const h16x4 h = {(h16)(o[t][0] * inv), (h16)(o[t][1] * inv), (h16)(o[t][2] * inv), (h16)(o[t][3] * inv)};
       *reinterpret_cast<h16x4*>(op + 16 * t) = h;
     }
   }
+}
+
+template <int D, bool SPLIT = false, bool COOP = false, bool PACK = false>
+__global__ void __launch_bounds__(WAVES * 64) pa_prefill_kernel(const Params p) {
+  prefill_tile<D, SPLIT, COOP, PACK, false>(p);
+}
+template <int D>
+__global__ void __launch_bounds__(WAVES * 64) pa_prefill_prefix_kernel(const Params p) {
+  prefill_tile<D, true, true, false, true>(p);
 }
 
 }  // namespace prefill

@@ -46,6 +46,7 @@ struct ParamsFp8 {
   float* ws;
   int32_t part_tokens, num_parts, groups;
   int32_t g_shift;              // the head-packed form only: log2 q_per_kv
+  int32_t part0;                // the suffix launch of the shared-prefix form only: the grid's first partition (else 0)
 };
 
 // four E4M3 bytes -> four halves (two dwords of half pairs), element order kept
@@ -65,62 +66,48 @@ __device__ __forceinline__ h16x8 e4m3x8_to_h16x8(uint32_t w0, uint32_t w1) {
 // on the still unscaled triples; the barrier rule is written there); PACK: its head-packed form (column n = row j0 + (n >> log2 G),
 // query head kvh * G + (n & (G - 1)); one always-cooperative tile per workgroup, x = ((part * tiles + tile_rev) * num_seqs + seq) *
 // num_kv_heads + kvh) — a block is then fetched and DECODED once per KV head, not once per query head.  The permuted k index
-// is a matter of dims alone: it stays as it is.
-template <int D, bool SPLIT = false, bool COOP = false, bool PACK = false>
-__global__ void __launch_bounds__(WAVES * 64) pa_prefill_fp8_kernel(const ParamsFp8 p) {
+// is a matter of dims alone: it stays as it is.  PREFIX: its shared-prefix form (pa_prefill_prefix_fp8_kernel<D>, below: column n =
+// row 16 * tile + n of the packed batch, one walk of the prefix through row 0 of block_tables, partition 0's partials WITHOUT
+// kv_scale; the barrier rule and the skipped select are written there) — a prefix block is then decoded once per tile of sixteen
+// rows, not once per (sequence, head).
+template <int D, bool SPLIT, bool COOP, bool PACK, bool PREFIX>
+__device__ __forceinline__ void prefill_tile_fp8(const ParamsFp8& p) {
   static_assert(COOP || !PACK, "the head-packed form is cooperative by construction");
+  static_assert(!PREFIX || (SPLIT && COOP && !PACK), "the shared-prefix form is a cooperative tile of partition 0, one query head");
   constexpr int KG = D / 64;    // 64-dim groups of a K block: one 16-byte load, two MFMAs each
   constexpr int VT = D / 16;    // 16-dim tiles of the output: one dword per block, one MFMA each
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int nh = PACK ? p.num_heads >> p.g_shift : p.num_heads;   // x's innermost axis: query heads, or — packed — KV heads
-  const int items = p.num_seqs * nh;
-  const int slot = blockIdx.x / items;
-  const int rem = blockIdx.x - slot * items;
-  const int seq = rem / nh, hx = rem - seq * nh;
-  const int part = SPLIT ? slot / p.groups : 0;      // my context partition: tokens part * part_tokens .. + part_tokens - 1
-  const int grev = SPLIT ? slot - part * p.groups : slot;
-  int row_lo, q_len, L;
-  if (!seq_span(p, seq, row_lo, q_len, L)) return;
-  const int ctx = L - q_len;    // cached positions in front of the chunk
-  const int ngroups = PACK ? (q_len + (TILE >> p.g_shift) - 1) >> (4 - p.g_shift) : (q_len + ROWS - 1) / ROWS;   // packed: R-row tiles
-  if (grev >= ngroups) return;
-  int j0 = PACK ? (ngroups - 1 - grev) << (4 - p.g_shift)
-                : ((ngroups - 1 - grev) * WAVES + wave) * TILE;   // first row of my tile within the chunk
-  bool coop = PACK;                                               // (workgroup-uniform)
-  if constexpr (COOP && !PACK) {
-    coop = q_len - (ngroups - 1 - grev) * ROWS <= TILE;           // my group's live rows fit one tile: all four waves take it
-    if (coop) j0 = (ngroups - 1 - grev) * ROWS;
-  }
-  if (!coop && j0 >= q_len) return;                               // (wave-uniform; never taken by a cooperating workgroup)
-
   const int n = lane & 15, kg = lane >> 4;
-  const int r = PACK ? n >> p.g_shift : n;               // my column's row within the tile, and its query head
-  const int head = PACK ? (hx << p.g_shift) + (n & ((1 << p.g_shift) - 1)) : hx;
-  const int jr = min(j0 + r, q_len - 1);                 // rows past the chunk repeat its last row and are not stored
-  const int pos = ctx + jr;                              // my column's position: it attends to tokens 0..pos
-  const int last_pos = ctx + min(j0 + (PACK ? TILE >> p.g_shift : TILE) - 1, q_len - 1);
+  Column col;
+  if constexpr (PREFIX) {
+    if (!prefix_column(p, n, col)) return;                 // (workgroup-uniform)
+  } else {
+    if (!chunk_column<SPLIT, COOP, PACK>(p, wave, n, col)) return;
+  }
+  const int part = col.part, head = col.head, pos = col.pos, last_pos = col.last_pos;
+  const bool coop = col.coop;
   const int nblk = last_pos / BS + 1, npair = (nblk + 1) >> 1;
   // the trips I walk: all of them, or my partition's (it starts on a pair boundary; a tile that ends below it leaves)
   int pp0 = 0, pp1 = npair;
-  if constexpr (SPLIT) {
+  if constexpr (SPLIT && !PREFIX) {
     if (last_pos < part * p.part_tokens) return;           // (wave-uniform; workgroup-uniform when cooperating)
     pp0 = part * (p.part_tokens >> 5);
     pp1 = min(npair, pp0 + (p.part_tokens >> 5));
   }
 
   // Q^T in the permuted k order of the K operand: for MFMA (g, j) dims 64g + 16kg + 8j .. +7
-  const h16* qp = p.q + (int64_t)(row_lo + jr) * p.q_stride + (int64_t)head * D + 16 * kg;
+  const h16* qp = p.q + (int64_t)col.q_row * p.q_stride + (int64_t)head * D + 16 * kg;
   h16x8 qB[KG][2];
 #pragma unroll
   for (int g = 0; g < KG; ++g)
 #pragma unroll
     for (int j = 0; j < 2; ++j) qB[g][j] = *reinterpret_cast<const h16x8*>(qp + 64 * g + 8 * j);
 
-  const int64_t head_off = (int64_t)(PACK ? hx : head / p.q_per_kv) * p.kv_head_stride;
+  const int64_t head_off = (int64_t)col.kv_head * p.kv_head_stride;
   const uint8_t* kbase = p.kc + head_off + 16 * lane;
   const uint8_t* vbase = p.vc + head_off + n * BS + 4 * kg;
-  const int32_t* bt = p.block_tables + (int64_t)seq * p.max_blocks_per_seq;
+  const int32_t* bt = p.block_tables + (int64_t)col.table_row * p.max_blocks_per_seq;
 
   // a pair's physical blocks; the absent second block of an odd count re-reads the first (its tokens are masked)
   auto phys_of = [&](int pp, int i) -> int64_t {
@@ -177,6 +164,11 @@ __global__ void __launch_bounds__(WAVES * 64) pa_prefill_fp8_kernel(const Params
         acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(e4m3x8_to_h16x8(kcur[i][g][2], kcur[i][g][3]), qB[g][1], acc, 0, 0, 0);
       }
       const int tok0 = (2 * pp + i) * BS + 4 * kg;
+      if (PREFIX && !col.select) {   // (wave-uniform: every column of the tile sees the whole prefix)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) mx = fmaxf(mx, s[i][r] = acc[r] * p.scale_log2e);
+        continue;
+      }
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         s[i][r] = (tok0 + r <= pos) ? acc[r] * p.scale_log2e : -INFINITY;
@@ -231,21 +223,33 @@ __global__ void __launch_bounds__(WAVES * 64) pa_prefill_fp8_kernel(const Params
       if (!coop_merge<D>(lds, wave, lane, o, m, lsum)) return;
     }
   }
+  const int r = PACK ? n >> p.g_shift : n;               // my column's row within the tile
+  const bool live = PREFIX ? col.live : r < col.live_rows;
+  const int out_row = PREFIX ? col.out_row : col.row0 + r;
   if constexpr (SPLIT) {
     // unnormalised partials of the columns that see a token of this partition (the others hold sum 0 and are never merged)
-    if (j0 + r < q_len && pos >= part * p.part_tokens)
-      store_partial<D>(p.ws, p.num_tokens, p.num_heads, p.num_parts, part, row_lo + j0 + r, head, kg, o, m, lsum);
+    if (live && pos >= part * p.part_tokens)
+      store_partial<D>(p.ws, p.num_tokens, p.num_heads, p.num_parts, part, out_row, head, kg, o, m, lsum);
     return;
   }
-  if (j0 + r < q_len) {
+  if (live) {
     const float inv = p.kv_scale / lsum;   // (a stored row attends at least to token 0: lsum >= 1)
-    h16* op = p.out + ((int64_t)(row_lo + j0 + r) * p.num_heads + head) * D + 4 * kg;
+    h16* op = p.out + ((int64_t)out_row * p.num_heads + head) * D + 4 * kg;
 #pragma unroll
     for (int t = 0; t < VT; ++t) {
       const h16x4 h = {(h16)(o[t][0] * inv), (h16)(o[t][1] * inv), (h16)(o[t][2] * inv), (h16)(o[t][3] * inv)};
       *reinterpret_cast<h16x4*>(op + 16 * t) = h;
     }
   }
+}
+
+template <int D, bool SPLIT = false, bool COOP = false, bool PACK = false>
+__global__ void __launch_bounds__(WAVES * 64) pa_prefill_fp8_kernel(const ParamsFp8 p) {
+  prefill_tile_fp8<D, SPLIT, COOP, PACK, false>(p);
+}
+template <int D>
+__global__ void __launch_bounds__(WAVES * 64) pa_prefill_prefix_fp8_kernel(const ParamsFp8 p) {
+  prefill_tile_fp8<D, true, true, false, true>(p);
 }
 
 }  // namespace prefill

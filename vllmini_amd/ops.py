@@ -602,6 +602,7 @@ def paged_attention_prefill(
     partition_tokens: Optional[int] = None,
     cooperative: Optional[bool] = False,
     pack_heads: Optional[bool] = False,
+    shared_prefix_len: Optional[int] = None,
 ) -> None:
     """Tiled causal attention of a chunk of query rows per sequence over the paged cache (extension: the reference runs its
     prefill as eager masked attention, gpt2.py:46-58); writes `out` in place, returns None.
@@ -632,13 +633,39 @@ def paged_attention_prefill(
     rows — walks its context once per KV head with full tiles, where the other forms walk it once per query head.  False
     (default): the launches above.  True: the packed ones, split or not by max_seq_len / partition_tokens through
     prefill_gqa_plan (without max_seq_len the block table's capacity stands in as the bound); `cooperative` is not consulted,
-    the form is cooperative by construction.  None: the measured rule, prefill_pack_heads_for — never without max_seq_len."""
+    the form is cooperative by construction.  None: the measured rule, prefill_pack_heads_for — never without max_seq_len.
+
+    `shared_prefix_len` = P attends a SHARED PROMPT PREFIX once per batch (cascade attention), for a batch whose sequences all
+    begin with the same system prompt or few-shot header.  Contract: the first P cached positions of every sequence of the call
+    are the same tokens in the same blocks; their block indices are read from ROW 0 of `block_tables` only — the first P / 16
+    entries of every other row are never read.  P is a positive multiple of 32, needs `max_seq_len` > P, and `partition_tokens`
+    must be None or P: the prefix is partition 0 of the split scheme.  Three launches: prefix tiles of 16 consecutive rows of the
+    packed batch x one head walk one copy of the prefix and write partition 0's partials, the partition kernels write every
+    sequence's own suffix from partition 1 on — in the form `cooperative` / `pack_heads` choose, as above — and the same merge
+    launch folds them.  The result is the unshared call's (same bound); only the route changes.  None (default): every launch
+    above, bit for bit.  There is no rule behind None: the library cannot see sharing, the caller says so.  Under stream
+    capture with no cached workspace large enough the unshared launch is taken (the per-sequence tables are valid).
+    Measured advice (profiles/prefill_prefix.md, MI355X, 256 one-row sequences): it pays for batches of one-row chunks from
+    P = 512 on (fp8 pages -16 % there, fp16 from longer prefixes: -29 % / -49 % at P = 2 048); it LOSES 12 - 27 % on chunks of 16 rows
+    and more, whose tiles are full already, and 9 - 71 % at P <= 128, where three launches stand against one."""
     if cooperative is not None and not isinstance(cooperative, bool):
         raise RuntimeError(f"paged_attention_prefill: cooperative must be True, False or None, got {cooperative!r}")
     if pack_heads is not None and not isinstance(pack_heads, bool):
         raise RuntimeError(f"paged_attention_prefill: pack_heads must be True, False or None, got {pack_heads!r}")
     if max_seq_len is None and partition_tokens is not None:
         raise RuntimeError("paged_attention_prefill: partition_tokens needs max_seq_len (the host-known bound on seq_lens)")
+    if shared_prefix_len is not None:
+        if isinstance(shared_prefix_len, bool) or not isinstance(shared_prefix_len, int) or shared_prefix_len <= 0 or \
+                shared_prefix_len % 32:
+            raise RuntimeError(f"paged_attention_prefill: shared_prefix_len must be a positive multiple of 32, got {shared_prefix_len!r}")
+        if max_seq_len is None:
+            raise RuntimeError("paged_attention_prefill: shared_prefix_len needs max_seq_len (the host-known bound on seq_lens)")
+        if shared_prefix_len >= int(max_seq_len):
+            raise RuntimeError(f"paged_attention_prefill: shared_prefix_len={shared_prefix_len} must be less than "
+                               f"max_seq_len={max_seq_len}")
+        if partition_tokens is not None and int(partition_tokens) != shared_prefix_len:
+            raise RuntimeError(f"paged_attention_prefill: partition_tokens={partition_tokens} must be None or equal "
+                               f"shared_prefix_len={shared_prefix_len} (the prefix is partition 0)")
     fp8 = _check_kv_cache_dtype(kv_cache_dtype)     # first: an unknown or unbuilt dtype is reported whatever the tensors are
     if fp8 == 2:
         raise RuntimeError(f"paged_attention_prefill is not built for E5M2 pages (kv_cache_dtype='{kv_cache_dtype}'); "
@@ -716,7 +743,17 @@ def paged_attention_prefill(
     coop = cooperative
     if coop is None and not pack:
         coop = max_seq_len is not None and prefill_cooperative_for(max_q_len, max_seq_len, num_seqs, num_heads, _num_cus(index))
-    if (coop or pack) and max_seq_len is None:          # one cooperative launch, bounded by what the block table can hold
+    prefix_ws = None
+    if shared_prefix_len is not None:                   # the prefix is partition 0: the split plan's workspace for PT = P
+        nbytes = prefill_split_plan(num_tokens, num_heads, head_size, num_seqs, max_q_len, max_seq_len, _num_cus(index),
+                                    shared_prefix_len)[2]
+        prefix_ws = prefill_workspace_for(index, nbytes, args[-1])   # None: capturing without one — the unshared launch below
+    if prefix_ws is not None:
+        tail = (int(max_seq_len), shared_prefix_len, prefix_ws.data_ptr(), prefix_ws.numel())
+        form = (shared_prefix_len, 2 if pack else 1 if coop else 0)
+        rc = lib.vmi_paged_attention_prefill_prefix_fp8(*args, *tail, float(kv_scale), *form) if fp8 else \
+            lib.vmi_paged_attention_prefill_prefix_f16(*args, *tail, *form)
+    elif (coop or pack) and max_seq_len is None:        # one cooperative launch, bounded by what the block table can hold
         bound = min(16 * ts[1], 2 ** 31 - 32)
         tail = (bound, max(32, (bound + 31) // 32 * 32), None, 0)
         form = "gqa" if pack else "coop"
