@@ -586,6 +586,50 @@ int vmi_paged_attention_prefill_prefix_fp8(
     int32_t shared_prefix_len, int32_t suffix_form);
 
 /*
+ * The same operator with the two score terms that are functions of t - pos (added under ABI 22 like the entries above): ALiBi
+ * slopes and a sliding window.  The row at cached position pos of head h attends the tokens t with pos - W < t <= pos and scores
+ * them scale * q . k + alibi_slopes[h] * (t - pos).  Kernels: the REL form in vllmini_amd/csrc/pa_prefill.hpp / pa_prefill_fp8.hpp
+ * (pa_prefill_rel_kernel / pa_prefill_rel_fp8_kernel) and pa_prefill_merge_rel_kernel (pa_prefill_split.hpp); the entries above
+ * launch what they launched before.  Arguments and validation are vmi_paged_attention_prefill_split_f16's / _fp8's, and in addition:
+ *   alibi_slopes     device pointer to num_heads floats, or NULL: no ALiBi term.  For fp8 pages the term is not scaled by kv_scale.
+ *   sliding_window   W > 0; 0: no window; negative: VMI_E_SHAPE.  W >= seq_len is plain causal attention.
+ *   form             0: the plain tiles, 1: the cooperative ones, 2: the head-packed ones (num_heads / num_kv_heads in {2, 4, 8, 16},
+ *                    else VMI_E_KV_HEADS); anything else VMI_E_SHAPE.
+ * THE WINDOW CONTRACT: with lo = max(0, seq_len - q_len - W + 1) — the window start of a sequence's first row — the blocks that lie
+ * wholly below lo are never read: neither their block_tables entries nor their K / V bytes, which may hold anything (NaN
+ * patterns included).  With a window the partitions of a sequence count from lo & ~31, and their number, the grid and the
+ * workspace are those of a context of min(max_seq_len, W + max_q_len - 1) tokens: partition_tokens and workspace_bytes are
+ * checked against vmi_paged_attention_prefill_rel_plan(..., partition_tokens_in = partition_tokens).  Fixed orders, no atomics:
+ * run-to-run bit-identical.  A shared prefix together with either term is not built.
+ */
+int vmi_paged_attention_prefill_rel_f16(
+    void* out, const void* query, const void* key_cache, const void* value_cache,
+    int32_t num_tokens, int32_t num_heads, int32_t head_size, int32_t num_kv_heads, float scale,
+    const int32_t* block_tables, const int32_t* seq_lens, const int32_t* cu_q_lens,
+    int32_t num_seqs, int32_t max_q_len, int32_t block_size, int32_t max_num_blocks_per_seq,
+    int64_t q_stride, int64_t kv_block_stride, int64_t kv_head_stride, int32_t device, void* stream,
+    int32_t max_seq_len, int32_t partition_tokens, void* workspace, int64_t workspace_bytes,
+    const float* alibi_slopes, int32_t sliding_window, int32_t form);
+int vmi_paged_attention_prefill_rel_fp8(
+    void* out, const void* query, const void* key_cache, const void* value_cache,
+    int32_t num_tokens, int32_t num_heads, int32_t head_size, int32_t num_kv_heads, float scale,
+    const int32_t* block_tables, const int32_t* seq_lens, const int32_t* cu_q_lens,
+    int32_t num_seqs, int32_t max_q_len, int32_t block_size, int32_t max_num_blocks_per_seq,
+    int64_t q_stride, int64_t kv_block_stride, int64_t kv_head_stride, int32_t device, void* stream,
+    int32_t max_seq_len, int32_t partition_tokens, void* workspace, int64_t workspace_bytes, float kv_scale,
+    const float* alibi_slopes, int32_t sliding_window, int32_t form);
+
+/*
+ * Plan of the REL launch: vmi_paged_attention_prefill_split_plan's arguments, results and rule (same constants), evaluated on a
+ * context of min(max_seq_len, sliding_window + max_q_len - 1) tokens (sliding_window 0: on max_seq_len, the split plan's own
+ * answer), and for form 2 on the head-packed grid of vmi_paged_attention_prefill_gqa_plan (num_kv_heads is read for form 2 only).
+ */
+int vmi_paged_attention_prefill_rel_plan(
+    int32_t num_tokens, int32_t num_heads, int32_t head_size, int32_t num_seqs, int32_t max_q_len, int32_t max_seq_len,
+    int32_t num_cus, int32_t partition_tokens_in, int32_t* partition_tokens, int32_t* num_partitions,
+    int64_t* workspace_bytes, int32_t num_kv_heads, int32_t sliding_window, int32_t form);
+
+/*
  * The pool's preemption move (extension; counterpart of BlockManager.swap_to_cpu / swap_from_cpu,
  * vllmini/block_manager.py:70-87, which the reference runs as one copy per block, cache_kernels.cu:56-62): ONE launch on
  * `stream` moves block_mapping[i] = (src block, dst block) of BOTH caches for every i.

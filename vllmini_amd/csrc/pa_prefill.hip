@@ -9,6 +9,8 @@
 
 #include <limits.h>
 
+#include <type_traits>
+
 #include "pa_host.hpp"
 #include "vmi_paged_attention.h"
 
@@ -41,13 +43,18 @@ static int fail_pack_ratio(int32_t num_heads, int32_t num_kv_heads) {
 }
 
 // -> VMI_OK and (partition_tokens, num_partitions, workspace_bytes); num_partitions == 1: do not split, 0 bytes.
-// g_shift >= 0: the head-packed grid — ceil(max_q_len / R) tiles of R = 16 >> g_shift rows per (sequence, KV head)
+// g_shift >= 0: the head-packed grid — ceil(max_q_len / R) tiles of R = 16 >> g_shift rows per (sequence, KV head).
+// window > 0 (the REL entries): no row sees more than `window` tokens, a sequence's rows together at most window + max_q_len - 1
+// — the rule, the partitions and the workspace are sized on that depth where it is less than max_seq_len (the partitions then
+// count from each sequence's own window start: pa_prefill.hpp, Rel).
 static int split_plan(int32_t num_tokens, int32_t num_heads, int32_t head_size, int32_t num_seqs, int32_t max_q_len,
-                      int32_t max_seq_len, int32_t num_cus, int32_t partition_tokens_in, int32_t* partition_tokens,
-                      int32_t* num_partitions, int64_t* workspace_bytes, int g_shift = -1) {
+                      int32_t max_seq_len_in, int32_t num_cus, int32_t partition_tokens_in, int32_t* partition_tokens,
+                      int32_t* num_partitions, int64_t* workspace_bytes, int g_shift = -1, int32_t window = 0) {
+  int64_t max_seq_len = max_seq_len_in;
+  if (window > 0 && (int64_t)window + max_q_len - 1 < max_seq_len && max_q_len > 0) max_seq_len = (int64_t)window + max_q_len - 1;
   if (num_tokens < 0 || num_heads <= 0 || num_seqs < 0 || max_q_len < 0 || max_seq_len < 0 || num_cus <= 0)
     return fail(VMI_E_SHAPE, "paged_attention_prefill_split_plan: negative size (num_tokens=%d num_heads=%d num_seqs=%d "
-                "max_q_len=%d max_seq_len=%d num_cus=%d)", num_tokens, num_heads, num_seqs, max_q_len, max_seq_len, num_cus);
+                "max_q_len=%d max_seq_len=%d num_cus=%d)", num_tokens, num_heads, num_seqs, max_q_len, max_seq_len_in, num_cus);
   if (head_size != 64 && head_size != 128)
     return fail(VMI_E_HEAD_SIZE, "Unsupported head size: %d (paged_attention_prefill is built for 64 and 128)", head_size);
   if (partition_tokens_in < 0 || (partition_tokens_in & 31))
@@ -116,6 +123,31 @@ static void launch_prefix(const prefill::ParamsFp8& p, int head_size, dim3 grid,
   else
     hipLaunchKernelGGL(prefill::pa_prefill_prefix_fp8_kernel<128>, grid, block, 0, st, p);
 }
+// the REL kernels (ALiBi slopes / sliding window): twenty-four instantiations — two page formats x two head sizes x the plain,
+// SPLIT, COOP, SPLIT + COOP, PACK and PACK + SPLIT forms
+template <bool SPLIT, bool COOP, bool PACK>
+static void launch_rel_form(const prefill::RelParams& p, int head_size, dim3 grid, dim3 block, hipStream_t st) {
+  if (head_size == 64)
+    hipLaunchKernelGGL((prefill::pa_prefill_rel_kernel<64, SPLIT, COOP, PACK>), grid, block, 0, st, p);
+  else
+    hipLaunchKernelGGL((prefill::pa_prefill_rel_kernel<128, SPLIT, COOP, PACK>), grid, block, 0, st, p);
+}
+template <bool SPLIT, bool COOP, bool PACK>
+static void launch_rel_form(const prefill::RelParamsFp8& p, int head_size, dim3 grid, dim3 block, hipStream_t st) {
+  if (head_size == 64)
+    hipLaunchKernelGGL((prefill::pa_prefill_rel_fp8_kernel<64, SPLIT, COOP, PACK>), grid, block, 0, st, p);
+  else
+    hipLaunchKernelGGL((prefill::pa_prefill_rel_fp8_kernel<128, SPLIT, COOP, PACK>), grid, block, 0, st, p);
+}
+template <bool SPLIT, class P>
+static void launch_rel(const P& p, int head_size, bool coop, dim3 grid, dim3 block, hipStream_t st) {
+  if (p.g_shift >= 0)
+    launch_rel_form<SPLIT, true, true>(p, head_size, grid, block, st);
+  else if (coop)
+    launch_rel_form<SPLIT, true, false>(p, head_size, grid, block, st);
+  else
+    launch_rel_form<SPLIT, false, false>(p, head_size, grid, block, st);
+}
 template <bool SPLIT, class P>
 static void launch_tiles(const P& p, int head_size, bool coop, dim3 grid, dim3 block, hipStream_t st) {
   if (p.g_shift >= 0)
@@ -132,6 +164,8 @@ static void launch_tiles(const P& p, int head_size, bool coop, dim3 grid, dim3 b
 // prefix > 0 (the shared-prefix entries, which checked it: a multiple of 32, == partition_tokens, < max_seq_len — so there are
 // at least two partitions and a workspace): partition 0 comes from the PREFIX tiles, launched first; coop / pack then are the
 // form of the SUFFIX launch, whose partition axis starts at part0 = 1; the merge launch is the same.
+// rel (the REL entries, which checked window >= 0): the REL kernels of the same form with alibi_slopes (may be NULL) and window
+// (0: none); the plan counts on min(max_seq_len, window + max_q_len - 1), and the merge is the REL one.
 static int launch_pa_prefill(void* out, const void* query, const void* key_cache, const void* value_cache,
                              int32_t num_tokens, int32_t num_heads, int32_t head_size, int32_t num_kv_heads, float scale,
                              const int32_t* block_tables, const int32_t* seq_lens, const int32_t* cu_q_lens,
@@ -139,7 +173,8 @@ static int launch_pa_prefill(void* out, const void* query, const void* key_cache
                              int64_t q_stride, int64_t kv_block_stride, int64_t kv_head_stride, int32_t device,
                              void* stream, bool fp8, float kv_scale, int32_t max_seq_len = -1,
                              int32_t partition_tokens = 0, void* workspace = nullptr, int64_t workspace_bytes = 0,
-                             bool coop = false, bool pack = false, int32_t prefix = 0) {
+                             bool coop = false, bool pack = false, int32_t prefix = 0, bool rel = false,
+                             const float* alibi_slopes = nullptr, int32_t window = 0) {
   // one validation for both page formats; the cache strides are in cache elements: halves, or bytes when fp8
   const bool empty = num_tokens == 0 || num_seqs == 0;   // (torch hands out null data pointers for empty tensors)
   if (!key_cache || !value_cache || (!empty && (!out || !query || !block_tables || !seq_lens || !cu_q_lens)))
@@ -175,7 +210,7 @@ static int launch_pa_prefill(void* out, const void* query, const void* key_cache
                   partition_tokens);
     int64_t need = 0;
     const int rc = split_plan(num_tokens, num_heads, head_size, num_seqs, max_q_len, max_seq_len, 1, partition_tokens,
-                              &partition_tokens, &parts, &need);
+                              &partition_tokens, &parts, &need, -1, window);
     if (rc != VMI_OK) return rc;
     if (parts > 1 && !empty && (!workspace || !aligned16(workspace) || workspace_bytes < need))
       return fail(VMI_E_WORKSPACE, "paged_attention_prefill: %d partitions need a 16-byte aligned workspace of %lld bytes (got %p, %lld bytes)",
@@ -227,6 +262,24 @@ static int launch_pa_prefill(void* out, const void* query, const void* key_cache
     p.part0 = 1;
     return hipGetLastError();
   };
+  // the REL kernels of either page format, split (std::true_type) or not: the same fields plus the two terms
+  auto rel_tiles = [&](auto split) {
+    auto go = [&](auto& p, float score_scale) {
+      fill(p);
+      p.scale_log2e = score_scale * 1.4426950408889634f;
+      p.alibi_slopes = alibi_slopes;
+      p.window = window;
+      launch_rel<decltype(split)::value>(p, head_size, coop, grid, block, st);
+    };
+    if (fp8) {
+      prefill::RelParamsFp8 p;
+      p.kv_scale = kv_scale;
+      go(p, scale * kv_scale);
+    } else {
+      prefill::RelParams p;
+      go(p, scale);
+    }
+  };
   if (parts > 1) {
     // partition kernels, then the merge, on the caller's stream: the second launch is the only synchronisation
     prefill::MergeParams mp;
@@ -242,7 +295,9 @@ static int launch_pa_prefill(void* out, const void* query, const void* key_cache
     mp.part_tokens = partition_tokens;
     mp.num_parts = parts;
     mp.out_scale = fp8 ? kv_scale : 1.0f;
-    if (fp8) {
+    if (rel) {
+      rel_tiles(std::true_type());
+    } else if (fp8) {
       prefill::ParamsFp8 p;
       fill(p);
       p.scale_log2e = (scale * kv_scale) * 1.4426950408889634f;
@@ -260,7 +315,15 @@ static int launch_pa_prefill(void* out, const void* query, const void* key_cache
     if (e != hipSuccess) return hip_fail(e, "paged_attention_prefill partition launch");
     const int rpb = 1024 / head_size;
     const dim3 mgrid((unsigned)(((int64_t)max_q_len + rpb - 1) / rpb * num_seqs * num_heads));
-    if (head_size == 64)
+    if (rel) {
+      prefill::MergeRelParams mrp;
+      static_cast<prefill::MergeParams&>(mrp) = mp;
+      mrp.window = window;
+      if (head_size == 64)
+        hipLaunchKernelGGL(prefill::pa_prefill_merge_rel_kernel<64>, mgrid, dim3(256), 0, st, mrp);
+      else
+        hipLaunchKernelGGL(prefill::pa_prefill_merge_rel_kernel<128>, mgrid, dim3(256), 0, st, mrp);
+    } else if (head_size == 64)
       hipLaunchKernelGGL(prefill::pa_prefill_merge_kernel<64>, mgrid, dim3(256), 0, st, mp);
     else
       hipLaunchKernelGGL(prefill::pa_prefill_merge_kernel<128>, mgrid, dim3(256), 0, st, mp);
@@ -268,7 +331,9 @@ static int launch_pa_prefill(void* out, const void* query, const void* key_cache
     if (e != hipSuccess) return hip_fail(e, "paged_attention_prefill merge launch");
     return VMI_OK;
   }
-  if (fp8) {
+  if (rel) {
+    rel_tiles(std::false_type());
+  } else if (fp8) {
     prefill::ParamsFp8 p;
     fill(p);
     p.scale_log2e = (scale * kv_scale) * 1.4426950408889634f;   // K's kv_scale rides in the score scale (x 1.0f is exact)
@@ -481,4 +546,72 @@ extern "C" int vmi_paged_attention_prefill_prefix_fp8(
                                 q_stride, kv_block_stride, kv_head_stride, device, stream, true, kv_scale, max_seq_len,
                                 partition_tokens, workspace, workspace_bytes, suffix_form >= 1, suffix_form == 2,
                                 shared_prefix_len);
+}
+
+// the REL entries' own checks, in front of the common ones
+static int check_rel(int32_t max_seq_len, const float* alibi_slopes, int32_t sliding_window, int32_t form) {
+  if (max_seq_len < 0) return vmi::fail(VMI_E_SHAPE, "paged_attention_prefill: negative max_seq_len=%d", max_seq_len);
+  if (sliding_window < 0)
+    return vmi::fail(VMI_E_SHAPE, "paged_attention_prefill: sliding_window must be positive (0: none), got %d", sliding_window);
+  if (form < 0 || form > 2)
+    return vmi::fail(VMI_E_SHAPE, "paged_attention_prefill: form must be 0 (plain), 1 (cooperative) or 2 (head-packed), got %d", form);
+  if (reinterpret_cast<uintptr_t>(alibi_slopes) & 3u)
+    return vmi::fail(VMI_E_ALIGNMENT, "paged_attention_prefill: alibi_slopes must be 4-byte aligned");
+  return VMI_OK;
+}
+
+extern "C" int vmi_paged_attention_prefill_rel_f16(
+    void* out, const void* query, const void* key_cache, const void* value_cache,
+    int32_t num_tokens, int32_t num_heads, int32_t head_size, int32_t num_kv_heads, float scale,
+    const int32_t* block_tables, const int32_t* seq_lens, const int32_t* cu_q_lens,
+    int32_t num_seqs, int32_t max_q_len, int32_t block_size, int32_t max_num_blocks_per_seq,
+    int64_t q_stride, int64_t kv_block_stride, int64_t kv_head_stride, int32_t device, void* stream,
+    int32_t max_seq_len, int32_t partition_tokens, void* workspace, int64_t workspace_bytes,
+    const float* alibi_slopes, int32_t sliding_window, int32_t form) {
+  const int rc = check_rel(max_seq_len, alibi_slopes, sliding_window, form);
+  if (rc != VMI_OK) return rc;
+  return vmi::launch_pa_prefill(out, query, key_cache, value_cache, num_tokens, num_heads, head_size, num_kv_heads, scale,
+                                block_tables, seq_lens, cu_q_lens, num_seqs, max_q_len, block_size, max_num_blocks_per_seq,
+                                q_stride, kv_block_stride, kv_head_stride, device, stream, false, 1.0f, max_seq_len,
+                                partition_tokens, workspace, workspace_bytes, form >= 1, form == 2, 0, true, alibi_slopes,
+                                sliding_window);
+}
+
+extern "C" int vmi_paged_attention_prefill_rel_fp8(
+    void* out, const void* query, const void* key_cache, const void* value_cache,
+    int32_t num_tokens, int32_t num_heads, int32_t head_size, int32_t num_kv_heads, float scale,
+    const int32_t* block_tables, const int32_t* seq_lens, const int32_t* cu_q_lens,
+    int32_t num_seqs, int32_t max_q_len, int32_t block_size, int32_t max_num_blocks_per_seq,
+    int64_t q_stride, int64_t kv_block_stride, int64_t kv_head_stride, int32_t device, void* stream,
+    int32_t max_seq_len, int32_t partition_tokens, void* workspace, int64_t workspace_bytes, float kv_scale,
+    const float* alibi_slopes, int32_t sliding_window, int32_t form) {
+  const int rc = check_rel(max_seq_len, alibi_slopes, sliding_window, form);
+  if (rc != VMI_OK) return rc;
+  return vmi::launch_pa_prefill(out, query, key_cache, value_cache, num_tokens, num_heads, head_size, num_kv_heads, scale,
+                                block_tables, seq_lens, cu_q_lens, num_seqs, max_q_len, block_size, max_num_blocks_per_seq,
+                                q_stride, kv_block_stride, kv_head_stride, device, stream, true, kv_scale, max_seq_len,
+                                partition_tokens, workspace, workspace_bytes, form >= 1, form == 2, 0, true, alibi_slopes,
+                                sliding_window);
+}
+
+extern "C" int vmi_paged_attention_prefill_rel_plan(
+    int32_t num_tokens, int32_t num_heads, int32_t head_size, int32_t num_seqs, int32_t max_q_len, int32_t max_seq_len,
+    int32_t num_cus, int32_t partition_tokens_in, int32_t* partition_tokens, int32_t* num_partitions,
+    int64_t* workspace_bytes, int32_t num_kv_heads, int32_t sliding_window, int32_t form) {
+  if (!partition_tokens || !num_partitions || !workspace_bytes)
+    return vmi::fail(VMI_E_NULL_POINTER, "paged_attention_prefill_rel_plan: NULL result pointer");
+  const int rc = check_rel(0, nullptr, sliding_window, form);
+  if (rc != VMI_OK) return rc;
+  const int g_shift = form == 2 ? vmi::pack_shift(num_heads, num_kv_heads) : -1;
+  if (form == 2 && g_shift < 0) return vmi::fail_pack_ratio(num_heads, num_kv_heads);
+  if (num_cus == 0) {   // ask the current device
+    int dev = 0;
+    hipDeviceProp_t prop;
+    hipError_t e = hipGetDevice(&dev);
+    if (e == hipSuccess) e = hipGetDeviceProperties(&prop, dev);
+    if (e != hipSuccess) return vmi::hip_fail(e, "paged_attention_prefill_rel_plan: device properties");
+    num_cus = prop.multiProcessorCount;
+  }
+  return vmi::split_plan(num_tokens, num_heads, head_size, num_seqs, max_q_len, max_seq_len, num_cus, partition_tokens_in,
+                         partition_tokens, num_partitions, workspace_bytes, g_shift, sliding_window);
 }

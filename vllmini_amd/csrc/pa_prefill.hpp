@@ -71,6 +71,11 @@ struct Params {
   // the suffix launch behind the shared-prefix tiles only (PREFIX, see below); 0 in every other launch
   int32_t part0;                // the grid's first partition: its partition axis counts num_parts - part0 from here
 };
+// The REL kernels' argument (a type of its own: the other kernels' argument block stays what it is)
+struct RelParams : Params {
+  const float* alibi_slopes;    // [num_heads] fp32, or NULL
+  int32_t window;               // W of the sliding window, 0: none
+};
 
 // THE guard of every kernel of the operator (unsplit, partition form, merge): a sequence with nothing to do, or with
 // lengths the tensors cannot hold or the host did not plan for, writes nothing.  -> false: leave.
@@ -244,6 +249,74 @@ __device__ __forceinline__ bool prefix_column(const P& p, int n, Column& c) {
   return true;
 }
 
+// What the REL form (the kernels' comment below) adds to a column's state, over both page formats.  Two terms, both functions of
+// t - pos: the row at pos sees tokens wlo = max(0, pos - W + 1) .. pos, and token t scores slope * (t - pos) on top of scale * q . k.
+// Per COLUMN: wlo, slope (log2 domain; packed tiles hold several heads).  Per TILE (wave-uniform): lo = the window start of its
+// first row — nothing below it is loaded, V below it is cleared; hi_lo = the window start of its last row — pairs that begin
+// at or above it hold no token below any column's window; first_pos — pairs that end at or below it hold none above any column's
+// diagonal.  base = the pair-aligned window start of the SEQUENCE's first row: its partitions count from there.
+struct Rel {
+  int wlo, lo, hi_lo, first_pos, base;
+  float slope;
+  template <class P>
+  __device__ __forceinline__ void init(const P& p, const Column& c) {
+    const int win = p.window > 0 ? p.window : 0x7fffffff;   // (pos - win + 1 >= 2 - 2^31: no overflow)
+    // the column map (chunk_column, which REL leaves as it is) holds both implicitly: a column is q_row - row0 rows past the
+    // tile's first row, so pos - (q_row - row0) is the tile's first position in all 64 lanes; and the guard passed, so the
+    // sequence's two lengths can be read again
+    first_pos = __builtin_amdgcn_readfirstlane(c.pos - (c.q_row - c.row0));
+    const int ctx = p.seq_lens[c.table_row] - (p.cu_q_lens[c.table_row + 1] - p.cu_q_lens[c.table_row]);
+    wlo = max(0, c.pos - win + 1);
+    lo = max(0, first_pos - win + 1);
+    hi_lo = max(0, c.last_pos - win + 1);
+    base = max(0, ctx - win + 1) & ~31;
+    slope = p.alibi_slopes ? p.alibi_slopes[c.head] * 1.4426950408889634f : 0.f;
+  }
+  // The pairs [pp0, pp1) the tile walks (on entry: [0, npair)); -> false: leave.  SPLIT: partition `part` covers tokens
+  // [base + part * PT, base + (part + 1) * PT) — the LAST one has no upper end: base is rounded down to a pair, so a sequence's
+  // span can exceed the planned W + max_q_len - 1 tokens by up to 31.  Every form starts no lower than the pair of `lo`; a
+  // partition wholly below it, or wholly above the tile, leaves.  All of it is wave-uniform, and workgroup-uniform when the
+  // four waves share the tile.
+  template <bool SPLIT, class P>
+  __device__ __forceinline__ bool bounds(const P& p, int part, int last_pos, int npair, int& pp0, int& pp1) const {
+    if constexpr (SPLIT) {
+      const int start = base + part * p.part_tokens;
+      if (last_pos < start) return false;
+      pp0 = start >> 5;
+      if (part < p.num_parts - 1) pp1 = min(npair, pp0 + (p.part_tokens >> 5));
+    }
+    pp0 = max(pp0, lo >> 5);
+    return pp0 < pp1;
+  }
+  // SPLIT: does the column at `pos` own partition `part`, i.e. see one of its tokens?  Partitions of wlo .. of pos, by
+  // arithmetic — the merge (pa_prefill_split.hpp) counts the same way.  (wlo >= base: pos >= ctx.)
+  template <class P>
+  __device__ __forceinline__ bool owns(const P& p, int part, int pos) const {
+    const int top = p.num_parts - 1;
+    return part >= min((wlo - base) / p.part_tokens, top) && part <= min((pos - base) / p.part_tokens, top);
+  }
+  // does pair pp hold a token outside some column's (window start, pos]?  (wave-uniform)
+  __device__ __forceinline__ bool edge(int pp) const { return 32 * pp < hi_lo || 32 * pp + 31 > first_pos; }
+  // the fp32 scores of tokens tok0 .. tok0 + 3 = pos + d0 .. : one FMA each on the exact distance; on an edge pair the
+  // SELECTED -inf outside [wlo, pos] (a K row below the window may be NaN: nothing of it survives the select); -> their maximum
+  __device__ __forceinline__ float scores(float (&s)[4], const f32x4& acc, float scale, float d0, int tok0, int pos, bool on_edge) const {
+    float mx = -INFINITY;
+    if (on_edge) {   // (wave-uniform)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float x = __builtin_fmaf(slope, d0 + (float)r, acc[r] * scale);
+        mx = fmaxf(mx, s[r] = (unsigned)(tok0 + r - wlo) <= (unsigned)(pos - wlo) ? x : -INFINITY);
+      }
+    } else {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) mx = fmaxf(mx, s[r] = __builtin_fmaf(slope, d0 + (float)r, acc[r] * scale));
+    }
+    return mx;
+  }
+  // how many of the four tokens tok0 .. tok0 + 3 lie below the tile's window start
+  __device__ __forceinline__ int below(int tok0) const { return min(max(lo - tok0, 0), 4); }
+};
+
 // Grid: one workgroup per (64-row group, sequence, head), x = group_rev * (num_seqs * num_heads) + seq * num_heads + head.
 // group_rev counts a sequence's groups from its LAST one, so the first num_seqs * num_heads workgroups of the launch are
 // every sequence's longest causal range; a sequence with fewer groups than the host bound leaves the surplus at once.
@@ -296,10 +369,30 @@ __device__ __forceinline__ bool prefix_column(const P& p, int n, Column& c) {
 // normal case — the select is skipped, wave-uniformly.  Grid: x = tile * num_heads + head, tiles = ceil(num_tokens / 16):
 // neighbours in x are the heads of one tile, so the heads of a KV head read the same pages at the same time.  (Packing them
 // into one tile, as PACK does, is the follow-up.)
-template <int D, bool SPLIT, bool COOP, bool PACK, bool PREFIX>
-__device__ __forceinline__ void prefill_tile(const Params& p) {
+//
+// REL (ALiBi slopes and a sliding window — two terms in t - pos — on the plain, SPLIT, COOP and PACK forms; kernels
+// pa_prefill_rel_kernel, argument RelParams; never with PREFIX): the row at pos sees tokens pos - W < t <= pos and token t scores
+// scale * q . k + slope[head] * (t - pos).  The state is struct Rel, above.  WALK: a tile's first pair is the pair of lo, the
+// window start of its first row, or its partition's first pair if that is higher; cooperating waves interleave from there.
+// Block-table entries and K / V bytes of blocks wholly below lo are never read: the half of the first pair that lies below lo
+// re-reads the other block, as the absent half of an odd last pair does, and its tokens are masked.  MASKS: only the first pairs of
+// a walk can hold a token below some column's window (those that begin below hi_lo) and only the last ones a token above some
+// column's pos (those that end above first_pos); Rel::edge() tells, wave-uniformly, and the pairs between run with no select at
+// all.  On an edge pair one unsigned comparison SELECTS -inf outside [wlo, pos] per column.  V elements below lo are cleared on
+// the raw bits in the tile's first pair — the last pair's clearing in reverse — so NaN bytes of a freed block never meet p = 0;
+// tokens between lo and a column's wlo are rows of the live window of an earlier row: finite, and they meet p = 0.  ALIBI:
+// fp32, log2 domain, on the relative distance — small where the weights are large: (float)(pair's first token - pos) once per
+// trip, the lane's token offsets added exactly, one FMA per score onto the scaled q . k (fp8 pages: kv_scale is in that scale
+// only).  SPLIT: partitions count from Rel::base, not from token 0 (Rel::bounds, Rel::owns); the host sizes their number from
+// min(max_seq_len, W + max_q_len - 1).  THE BARRIER RULE holds as before: REL adds one return in front of the barrier — a
+// partition wholly below the tile's window, in Rel::bounds — and it depends on (part, the tile's first and last position, W) alone,
+// which the four waves of a cooperating workgroup share; the loop still holds no exit.  A stored column sees at least itself:
+// its maximum contributes exp2(0), sum >= 1.
+template <int D, bool SPLIT, bool COOP, bool PACK, bool PREFIX, bool REL = false, class P = Params>
+__device__ __forceinline__ void prefill_tile(const P& p) {
   static_assert(COOP || !PACK, "the head-packed form is cooperative by construction");
   static_assert(!PREFIX || (SPLIT && COOP && !PACK), "the shared-prefix form is a cooperative tile of partition 0, one query head");
+  static_assert(!REL || !PREFIX, "ALiBi / sliding window over a shared prefix is not built");
   constexpr int KC = D / 32;    // 32-dim chunks of a K block: one MFMA each
   constexpr int VT = D / 16;    // 16-dim tiles of the output: one MFMA each
   const int lane = threadIdx.x & 63;
@@ -316,11 +409,16 @@ __device__ __forceinline__ void prefill_tile(const Params& p) {
   const int nblk = last_pos / BS + 1, npair = (nblk + 1) >> 1;
   // the trips I walk: all of them, or my partition's (it starts on a pair boundary; a tile that ends below it leaves)
   int pp0 = 0, pp1 = npair;
-  if constexpr (SPLIT && !PREFIX) {
+  Rel rel;
+  if constexpr (REL) {
+    rel.init(p, col);
+    if (!rel.template bounds<SPLIT>(p, part, last_pos, npair, pp0, pp1)) return;   // (wave-uniform; workgroup-uniform when cooperating)
+  } else if constexpr (SPLIT && !PREFIX) {
     if (last_pos < part * p.part_tokens) return;           // (wave-uniform; workgroup-uniform when cooperating)
     pp0 = part * (p.part_tokens >> 5);
     pp1 = min(npair, pp0 + (p.part_tokens >> 5));
   }
+  const int blk_lo = REL ? rel.lo / BS : 0;                // REL: the first block the tile may read
 
   const h16* qp = p.q + (int64_t)col.q_row * p.q_stride + (int64_t)head * D + 8 * kg;
   h16x8 qB[KC];
@@ -333,8 +431,10 @@ __device__ __forceinline__ void prefill_tile(const Params& p) {
   const int32_t* bt = p.block_tables + (int64_t)col.table_row * p.max_blocks_per_seq;
 
   // a pair's physical blocks; the absent second block of an odd count re-reads the first (its tokens are masked)
+  // (REL: nor is a block wholly below the tile's window read — the first pair's lower half re-reads the upper)
   auto phys_of = [&](int pp, int i) -> int64_t {
-    const int b = min(2 * pp + i, nblk - 1);
+    int b = min(2 * pp + i, nblk - 1);
+    if constexpr (REL) b = max(b, blk_lo);
     return (int64_t)__builtin_amdgcn_readfirstlane(bt[b]) * p.kv_block_stride;
   };
   auto load_k = [&](h16x8(&k)[2][KC], int pp) {
@@ -379,12 +479,18 @@ __device__ __forceinline__ void prefill_tile(const Params& p) {
     // ---- S^T = K . Q^T, scaled in fp32, causal mask selected ----
     float s[2][4];
     float mx = -INFINITY;
+    const bool on_edge = REL && rel.edge(pp);                                        // (wave-uniform)
+    const float dist = REL ? (float)(2 * pp * BS + 4 * kg - pos) : 0.f;             // REL: my first token's distance to my row
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int c = 0; c < KC; ++c) acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(kcur[i][c], qB[c], acc, 0, 0, 0);
       const int tok0 = (2 * pp + i) * BS + 4 * kg;
+      if constexpr (REL) {
+        mx = fmaxf(mx, rel.scores(s[i], acc, p.scale_log2e, dist + (float)(i * BS), tok0, pos, on_edge));
+        continue;
+      }
       if (PREFIX && !col.select) {   // (wave-uniform: every column of the tile sees the whole prefix)
 #pragma unroll
         for (int r = 0; r < 4; ++r) mx = fmaxf(mx, s[i][r] = acc[r] * p.scale_log2e);
@@ -427,6 +533,17 @@ __device__ __forceinline__ void prefill_tile(const Params& p) {
         for (int t = 0; t < VT; ++t) v[i][t] &= keep;
       }
     }
+    if constexpr (REL) {
+      if (pp == rel.lo >> 5) {   // the only trip that can hold tokens below the tile's window: clear them, from the low end
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+          const int nb = rel.below((2 * pp + i) * BS + 4 * kg);
+          const u32x2 keep = {nb >= 2 ? 0u : nb == 1 ? 0xffff0000u : 0xffffffffu, nb >= 4 ? 0u : nb == 3 ? 0xffff0000u : 0xffffffffu};
+#pragma unroll
+          for (int t = 0; t < VT; ++t) v[i][t] &= keep;
+        }
+      }
+    }
 #pragma unroll
     for (int t = 0; t < VT; ++t) {
       const u32x4 va = {v[0][t][0], v[0][t][1], v[1][t][0], v[1][t][1]};
@@ -451,6 +568,11 @@ __device__ __forceinline__ void prefill_tile(const Params& p) {
   const int out_row = PREFIX ? col.out_row : col.row0 + r;
   if constexpr (SPLIT) {
     // unnormalised partials of the columns that see a token of this partition (the others hold sum 0 and are never merged)
+    if constexpr (REL) {   // ... which here is a range of partitions with a lower end
+      if (live && rel.owns(p, part, pos))
+        store_partial<D>(p.ws, p.num_tokens, p.num_heads, p.num_parts, part, out_row, head, kg, o, m, lsum);
+      return;
+    }
     if (live && pos >= part * p.part_tokens)
       store_partial<D>(p.ws, p.num_tokens, p.num_heads, p.num_parts, part, out_row, head, kg, o, m, lsum);
     return;
@@ -473,6 +595,10 @@ __global__ void __launch_bounds__(WAVES * 64) pa_prefill_kernel(const Params p) 
 template <int D>
 __global__ void __launch_bounds__(WAVES * 64) pa_prefill_prefix_kernel(const Params p) {
   prefill_tile<D, true, true, false, true>(p);
+}
+template <int D, bool SPLIT = false, bool COOP = false, bool PACK = false>
+__global__ void __launch_bounds__(WAVES * 64) pa_prefill_rel_kernel(const RelParams p) {
+  prefill_tile<D, SPLIT, COOP, PACK, false, true>(p);
 }
 
 }  // namespace prefill

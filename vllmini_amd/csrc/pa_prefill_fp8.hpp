@@ -48,6 +48,10 @@ struct ParamsFp8 {
   int32_t g_shift;              // the head-packed form only: log2 q_per_kv
   int32_t part0;                // the suffix launch of the shared-prefix form only: the grid's first partition (else 0)
 };
+struct RelParamsFp8 : ParamsFp8 {   // the REL kernels' argument, as RelParams
+  const float* alibi_slopes;    // [num_heads] fp32, or NULL; the term is NOT scaled by kv_scale
+  int32_t window;               // W of the sliding window, 0: none
+};
 
 // four E4M3 bytes -> four halves (two dwords of half pairs), element order kept
 __device__ __forceinline__ u32x2 e4m3x4_to_h16x4(uint32_t w) {
@@ -69,11 +73,15 @@ __device__ __forceinline__ h16x8 e4m3x8_to_h16x8(uint32_t w0, uint32_t w1) {
 // is a matter of dims alone: it stays as it is.  PREFIX: its shared-prefix form (pa_prefill_prefix_fp8_kernel<D>, below: column n =
 // row 16 * tile + n of the packed batch, one walk of the prefix through row 0 of block_tables, partition 0's partials WITHOUT
 // kv_scale; the barrier rule and the skipped select are written there) — a prefix block is then decoded once per tile of sixteen
-// rows, not once per (sequence, head).
-template <int D, bool SPLIT, bool COOP, bool PACK, bool PREFIX>
-__device__ __forceinline__ void prefill_tile_fp8(const ParamsFp8& p) {
+// rows, not once per (sequence, head).  REL: its ALiBi / sliding-window form (pa_prefill_rel_fp8_kernel, argument RelParamsFp8:
+// walk bounds, edge-pair selects, relative partitions and the barrier rule are written there and shared through struct Rel); the
+// V bytes below the tile's window are cleared on the RAW dwords, before decoding, and the ALiBi term joins the score after
+// kv_scale: scale * kv_scale multiplies q . k alone.
+template <int D, bool SPLIT, bool COOP, bool PACK, bool PREFIX, bool REL = false, class P = ParamsFp8>
+__device__ __forceinline__ void prefill_tile_fp8(const P& p) {
   static_assert(COOP || !PACK, "the head-packed form is cooperative by construction");
   static_assert(!PREFIX || (SPLIT && COOP && !PACK), "the shared-prefix form is a cooperative tile of partition 0, one query head");
+  static_assert(!REL || !PREFIX, "ALiBi / sliding window over a shared prefix is not built");
   constexpr int KG = D / 64;    // 64-dim groups of a K block: one 16-byte load, two MFMAs each
   constexpr int VT = D / 16;    // 16-dim tiles of the output: one dword per block, one MFMA each
   const int lane = threadIdx.x & 63;
@@ -90,11 +98,16 @@ __device__ __forceinline__ void prefill_tile_fp8(const ParamsFp8& p) {
   const int nblk = last_pos / BS + 1, npair = (nblk + 1) >> 1;
   // the trips I walk: all of them, or my partition's (it starts on a pair boundary; a tile that ends below it leaves)
   int pp0 = 0, pp1 = npair;
-  if constexpr (SPLIT && !PREFIX) {
+  Rel rel;
+  if constexpr (REL) {
+    rel.init(p, col);
+    if (!rel.template bounds<SPLIT>(p, part, last_pos, npair, pp0, pp1)) return;   // (wave-uniform; workgroup-uniform when cooperating)
+  } else if constexpr (SPLIT && !PREFIX) {
     if (last_pos < part * p.part_tokens) return;           // (wave-uniform; workgroup-uniform when cooperating)
     pp0 = part * (p.part_tokens >> 5);
     pp1 = min(npair, pp0 + (p.part_tokens >> 5));
   }
+  const int blk_lo = REL ? rel.lo / BS : 0;                // REL: the first block the tile may read
 
   // Q^T in the permuted k order of the K operand: for MFMA (g, j) dims 64g + 16kg + 8j .. +7
   const h16* qp = p.q + (int64_t)col.q_row * p.q_stride + (int64_t)head * D + 16 * kg;
@@ -110,8 +123,10 @@ __device__ __forceinline__ void prefill_tile_fp8(const ParamsFp8& p) {
   const int32_t* bt = p.block_tables + (int64_t)col.table_row * p.max_blocks_per_seq;
 
   // a pair's physical blocks; the absent second block of an odd count re-reads the first (its tokens are masked)
+  // (REL: nor is a block wholly below the tile's window read — the first pair's lower half re-reads the upper)
   auto phys_of = [&](int pp, int i) -> int64_t {
-    const int b = min(2 * pp + i, nblk - 1);
+    int b = min(2 * pp + i, nblk - 1);
+    if constexpr (REL) b = max(b, blk_lo);
     return (int64_t)__builtin_amdgcn_readfirstlane(bt[b]) * p.kv_block_stride;
   };
   auto load_k = [&](u32x4(&k)[2][KG], int pp) {
@@ -155,6 +170,8 @@ __device__ __forceinline__ void prefill_tile_fp8(const ParamsFp8& p) {
     // ---- S^T = K . Q^T, scaled in fp32 (kv_scale included), causal mask selected ----
     float s[2][4];
     float mx = -INFINITY;
+    const bool on_edge = REL && rel.edge(pp);                                        // (wave-uniform)
+    const float dist = REL ? (float)(2 * pp * BS + 4 * kg - pos) : 0.f;             // REL: my first token's distance to my row
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -164,6 +181,10 @@ __device__ __forceinline__ void prefill_tile_fp8(const ParamsFp8& p) {
         acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(e4m3x8_to_h16x8(kcur[i][g][2], kcur[i][g][3]), qB[g][1], acc, 0, 0, 0);
       }
       const int tok0 = (2 * pp + i) * BS + 4 * kg;
+      if constexpr (REL) {
+        mx = fmaxf(mx, rel.scores(s[i], acc, p.scale_log2e, dist + (float)(i * BS), tok0, pos, on_edge));
+        continue;
+      }
       if (PREFIX && !col.select) {   // (wave-uniform: every column of the tile sees the whole prefix)
 #pragma unroll
         for (int r = 0; r < 4; ++r) mx = fmaxf(mx, s[i][r] = acc[r] * p.scale_log2e);
@@ -206,6 +227,17 @@ __device__ __forceinline__ void prefill_tile_fp8(const ParamsFp8& p) {
         for (int t = 0; t < VT; ++t) v[i][t] &= keep;
       }
     }
+    if constexpr (REL) {
+      if (pp == rel.lo >> 5) {   // the only trip that can hold tokens below the tile's window: clear their raw bytes, from the low end
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+          const int nb = rel.below((2 * pp + i) * BS + 4 * kg);
+          const uint32_t keep = nb >= 4 ? 0u : 0xffffffffu << (8 * nb);
+#pragma unroll
+          for (int t = 0; t < VT; ++t) v[i][t] &= keep;
+        }
+      }
+    }
 #pragma unroll
     for (int t = 0; t < VT; ++t)
       o[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(e4m3x8_to_h16x8(v[0][t], v[1][t]), pB, o[t], 0, 0, 0);
@@ -228,6 +260,11 @@ __device__ __forceinline__ void prefill_tile_fp8(const ParamsFp8& p) {
   const int out_row = PREFIX ? col.out_row : col.row0 + r;
   if constexpr (SPLIT) {
     // unnormalised partials of the columns that see a token of this partition (the others hold sum 0 and are never merged)
+    if constexpr (REL) {   // ... which here is a range of partitions with a lower end
+      if (live && rel.owns(p, part, pos))
+        store_partial<D>(p.ws, p.num_tokens, p.num_heads, p.num_parts, part, out_row, head, kg, o, m, lsum);
+      return;
+    }
     if (live && pos >= part * p.part_tokens)
       store_partial<D>(p.ws, p.num_tokens, p.num_heads, p.num_parts, part, out_row, head, kg, o, m, lsum);
     return;
@@ -250,6 +287,10 @@ __global__ void __launch_bounds__(WAVES * 64) pa_prefill_fp8_kernel(const Params
 template <int D>
 __global__ void __launch_bounds__(WAVES * 64) pa_prefill_prefix_fp8_kernel(const ParamsFp8 p) {
   prefill_tile_fp8<D, true, true, false, true>(p);
+}
+template <int D, bool SPLIT = false, bool COOP = false, bool PACK = false>
+__global__ void __launch_bounds__(WAVES * 64) pa_prefill_rel_fp8_kernel(const RelParamsFp8 p) {
+  prefill_tile_fp8<D, SPLIT, COOP, PACK, false, true>(p);
 }
 
 }  // namespace prefill

@@ -69,5 +69,50 @@ __global__ void __launch_bounds__(256) pa_prefill_merge_kernel(const MergeParams
   *reinterpret_cast<h16x4*>(p.out + item * D + 4 * c) = h;
 }
 
+// The merge behind the REL partition kernels (pa_prefill.hpp, REL: ALiBi slopes / a sliding window) — a kernel of its own, so
+// that the one above stays what it is.  Same grid, work split, arithmetic and order; what differs is WHICH partials a row has:
+// partitions count from the sequence's base = (window start of its first row) & ~31, the last one is open-ended, and the row
+// at pos has exactly those of max(0, pos - W + 1) .. of pos (Rel::owns stores by the same arithmetic).  No other word of the
+// workspace is read.
+struct MergeRelParams : MergeParams {
+  int32_t window;               // W of the sliding window, 0: none
+};
+
+template <int D>
+__global__ void __launch_bounds__(256) pa_prefill_merge_rel_kernel(const MergeRelParams p) {
+  constexpr int LPR = D / 4, RPB = 256 / LPR;
+  const int items = p.num_seqs * p.num_heads;
+  const int chunk = blockIdx.x / items;
+  const int rem = blockIdx.x - chunk * items;
+  const int seq = rem / p.num_heads, head = rem - seq * p.num_heads;
+  int row_lo, q_len, L;
+  if (!seq_span(p, seq, row_lo, q_len, L)) return;
+  const int j = chunk * RPB + (int)threadIdx.x / LPR;
+  if (j >= q_len) return;
+  const int c = (int)threadIdx.x % LPR;
+  const int win = p.window > 0 ? p.window : 0x7fffffff, pos = L - q_len + j;
+  const int base = max(0, L - q_len - win + 1) & ~31, top = p.num_parts - 1;
+  const int q0 = min((max(0, pos - win + 1) - base) / p.part_tokens, top);
+  const int np = min((pos - base) / p.part_tokens, top) + 1;
+
+  const int64_t item = (int64_t)(row_lo + j) * p.num_heads + head;
+  const int64_t pstride = (int64_t)p.num_tokens * p.num_heads;
+  const float* ml = p.ws + (int64_t)p.num_parts * pstride * D + item * 2;
+  const float* acc = p.ws + item * D + 4 * c;
+
+  float M = -INFINITY;
+  for (int q = q0; q < np; ++q) M = fmaxf(M, ml[q * pstride * 2]);
+  f32x4 o = f32x4{0.f, 0.f, 0.f, 0.f};
+  float den = 0.f;
+  for (int q = q0; q < np; ++q) {
+    const float w = __builtin_amdgcn_exp2f(ml[q * pstride * 2] - M);
+    o += *reinterpret_cast<const f32x4*>(acc + q * pstride * D) * w;
+    den += ml[q * pstride * 2 + 1] * w;
+  }
+  const float inv = p.out_scale / den;
+  const h16x4 h = {(h16)(o[0] * inv), (h16)(o[1] * inv), (h16)(o[2] * inv), (h16)(o[3] * inv)};
+  *reinterpret_cast<h16x4*>(p.out + item * D + 4 * c) = h;
+}
+
 }  // namespace prefill
 }  // namespace vmi

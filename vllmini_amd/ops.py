@@ -549,6 +549,22 @@ def prefill_gqa_plan(num_tokens: int, num_heads: int, head_size: int, num_seqs: 
     return pt.value, parts.value, nbytes.value
 
 
+def _prefill_rel_plan(num_tokens: int, num_heads: int, head_size: int, num_seqs: int, max_q_len: int, max_seq_len: int,
+                      num_cus: int, partition_tokens: int, num_kv_heads: int, sliding_window: int, form: int) -> tuple:
+    """The plan of the ALiBi / sliding-window launch: prefill_split_plan (form 2: prefill_gqa_plan) on a context of
+    min(max_seq_len, sliding_window + max_q_len - 1) tokens — no row sees more.  sliding_window 0: no window."""
+    import ctypes
+
+    pt, parts, nbytes = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int64()
+    rc = _lib.load().vmi_paged_attention_prefill_rel_plan(int(num_tokens), int(num_heads), int(head_size), int(num_seqs),
+                                                          int(max_q_len), int(max_seq_len), int(num_cus), int(partition_tokens),
+                                                          ctypes.byref(pt), ctypes.byref(parts), ctypes.byref(nbytes),
+                                                          int(num_kv_heads), int(sliding_window), int(form))
+    if rc != 0:
+        _raise_native(rc)
+    return pt.value, parts.value, nbytes.value
+
+
 PREFILL_PACK_RATIOS = (2, 4, 8, 16)
 
 
@@ -603,6 +619,8 @@ def paged_attention_prefill(
     cooperative: Optional[bool] = False,
     pack_heads: Optional[bool] = False,
     shared_prefix_len: Optional[int] = None,
+    alibi_slopes: Optional[torch.Tensor] = None,
+    sliding_window: Optional[int] = None,
 ) -> None:
     """Tiled causal attention of a chunk of query rows per sequence over the paged cache (extension: the reference runs its
     prefill as eager masked attention, gpt2.py:46-58); writes `out` in place, returns None.
@@ -647,7 +665,26 @@ def paged_attention_prefill(
     capture with no cached workspace large enough the unshared launch is taken (the per-sequence tables are valid).
     Measured advice (profiles/prefill_prefix.md, MI355X, 256 one-row sequences): it pays for batches of one-row chunks from
     P = 512 on (fp8 pages -16 % there, fp16 from longer prefixes: -29 % / -49 % at P = 2 048); it LOSES 12 - 27 % on chunks of 16 rows
-    and more, whose tiles are full already, and 9 - 71 % at P <= 128, where three launches stand against one."""
+    and more, whose tiles are full already, and 9 - 71 % at P <= 128, where three launches stand against one.
+
+    `alibi_slopes` (a contiguous float32 [num_heads] tensor on the query's device) and `sliding_window` = W (a positive int) add
+    the two score terms that are functions of t - pos, in every form above but the shared prefix and over both page formats (the REL
+    kernels, csrc/pa_prefill.hpp): the row at cached position pos of head h scores token t as scale * q . k + slopes[h] * (t - pos)
+    and attends the tokens pos - W < t <= pos — W of them, itself included; W >= seq_len is plain causal attention.  For fp8 pages
+    the ALiBi term is not scaled by kv_scale.  THE WINDOW CONTRACT: with lo = max(0, seq_len - q_len - W + 1), the window start of
+    the chunk's first row, blocks that lie wholly below lo are never read — neither their block_tables entries nor their K / V
+    bytes, which may hold anything: a caller may free them.  With a window the work is proportional to W: the walk starts at the
+    window, the partitions count from lo & ~31, and the split, cooperative and pack rules, the grid and the workspace are taken
+    on min(max_seq_len, W + max_q_len - 1) instead of max_seq_len.  Both None (default): every launch above, bit for bit, through
+    the same entries and kernels.  Either one together with `shared_prefix_len` raises: that combination is not built.
+    Measured (profiles/prefill_rel.md, MI355X): the ALiBi term costs +5 % on a float16 prefill of 64 prompts and nothing
+    measurable on decode rows; a window turns 38 into 12 - 17 us at 1 x 16 x 32 768 x 12 x 64 (W = 256 - 4 096) and 713 into 197 us for
+    256 decode rows over 4 096 tokens at W = 1 024; no measured cell lost."""
+    if sliding_window is not None and (isinstance(sliding_window, bool) or not isinstance(sliding_window, int) or sliding_window <= 0):
+        raise RuntimeError(f"paged_attention_prefill: sliding_window must be a positive int, got {sliding_window!r}")
+    rel = alibi_slopes is not None or sliding_window is not None
+    if rel and shared_prefix_len is not None:
+        raise RuntimeError("paged_attention_prefill: alibi_slopes / sliding_window together with shared_prefix_len is not built")
     if cooperative is not None and not isinstance(cooperative, bool):
         raise RuntimeError(f"paged_attention_prefill: cooperative must be True, False or None, got {cooperative!r}")
     if pack_heads is not None and not isinstance(pack_heads, bool):
@@ -676,10 +713,15 @@ def paged_attention_prefill(
         raise RuntimeError(f"query must be [num_tokens, num_heads, head_size], got {tuple(qs)}")
     if query.dtype != torch.float16:
         raise RuntimeError(f"Unsupported input type of paged attention prefill: {query.dtype} (float16 is built)")
+    if alibi_slopes is not None and (alibi_slopes.dtype != torch.float32 or alibi_slopes.numel() != qs[1] or
+                                     not alibi_slopes.is_contiguous()):
+        raise RuntimeError("alibi_slopes must be a contiguous float32 [num_heads] tensor")      # (_pa_common's check)
     index = query.get_device()
     dev = query.device
     if index < 0:
         _check_device("query", query, dev)
+    if alibi_slopes is not None:
+        _check_device("alibi_slopes", alibi_slopes, dev)
     _on("out", out, index, dev)
     _on("key_cache", key_cache, index, dev)
     _on("value_cache", value_cache, index, dev)
@@ -734,15 +776,38 @@ def paged_attention_prefill(
             block_tables.data_ptr(), seq_lens.data_ptr(), cu_q_lens.data_ptr(),
             num_seqs, int(max_q_len), block_size, ts[1], qst[0], kst[0], kst[1], index, _stream_of(index))
     lib = _lib.load()
+    window = min(int(sliding_window or 0), 2 ** 31 - 1)
+    rule_len = max_seq_len                              # what the rules behind None read: with a window, the depth a sequence's rows see
+    if window and max_seq_len is not None:
+        rule_len = min(int(max_seq_len), window + int(max_q_len) - 1)
     pack = pack_heads
     if pack is None:
-        pack = prefill_pack_heads_for(max_q_len, num_heads, num_kv_heads, max_seq_len, num_seqs, _num_cus(index))
+        pack = prefill_pack_heads_for(max_q_len, num_heads, num_kv_heads, rule_len, num_seqs, _num_cus(index))
     if pack and not _pack_ratio(num_heads, num_kv_heads):
         raise RuntimeError(f"paged_attention_prefill: pack_heads is built for num_heads / num_kv_heads in {PREFILL_PACK_RATIOS}, "
                            f"got num_heads={num_heads} num_kv_heads={num_kv_heads}")
     coop = cooperative
     if coop is None and not pack:
-        coop = max_seq_len is not None and prefill_cooperative_for(max_q_len, max_seq_len, num_seqs, num_heads, _num_cus(index))
+        coop = max_seq_len is not None and prefill_cooperative_for(max_q_len, rule_len, num_seqs, num_heads, _num_cus(index))
+    if rel:                                             # the REL kernels of the same form, planned on the windowed depth
+        form = 2 if pack else 1 if coop else 0
+        if max_seq_len is None:                         # one launch, bounded by what the block table can hold
+            bound = min(16 * ts[1], 2 ** 31 - 32)
+            tail = (bound, max(32, (bound + 31) // 32 * 32), None, 0)
+        else:
+            pt, parts, nbytes = _prefill_rel_plan(num_tokens, num_heads, head_size, num_seqs, max_q_len, max_seq_len,
+                                                  _num_cus(index), int(partition_tokens or 0), num_kv_heads, window, form)
+            ws = prefill_workspace_for(index, nbytes, args[-1]) if parts > 1 else None
+            if ws is None:                              # one partition (or capturing without a workspace): the single launch
+                tail = (int(max_seq_len), max(32, (int(max_seq_len) + 31) // 32 * 32), None, 0)
+            else:
+                tail = (int(max_seq_len), pt, ws.data_ptr(), ws.numel())
+        slopes = (_ptr(alibi_slopes), window, form)
+        rc = lib.vmi_paged_attention_prefill_rel_fp8(*args, *tail, float(kv_scale), *slopes) if fp8 else \
+            lib.vmi_paged_attention_prefill_rel_f16(*args, *tail, *slopes)
+        if rc != 0:
+            _raise_native(rc)
+        return None
     prefix_ws = None
     if shared_prefix_len is not None:                   # the prefix is partition 0: the split plan's workspace for PT = P
         nbytes = prefill_split_plan(num_tokens, num_heads, head_size, num_seqs, max_q_len, max_seq_len, _num_cus(index),
