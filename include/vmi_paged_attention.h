@@ -630,6 +630,40 @@ int vmi_paged_attention_prefill_rel_plan(
     int64_t* workspace_bytes, int32_t num_kv_heads, int32_t sliding_window, int32_t form);
 
 /*
+ * The cache write of a prefill CHUNK (extension; added under ABI 22 like the entries above): the bytes of
+ * vmi_reshape_and_cache_f16 / _fp8, addressed the way the tiled attention addresses them instead of by slot.  Sequence s owns
+ * rows cu_q_lens[s] .. cu_q_lens[s+1]-1 of key / value; row j sits at position pos = seq_lens[s] - q_len + j and goes to offset
+ * pos % 16 of block block_tables[s][pos / 16] — bit for bit what the slot entries write for slot = table[pos / 16] * 16 + pos % 16
+ * (fp8: the same conversion, float(x) / kv_scale in fp32, saturating, NaN kept).  No other byte of either cache changes.
+ * One wave per (sequence, block of the chunk's span, KV head): a block whose 16 offsets are all written goes out as whole
+ * contiguous tiles whatever packed row the sequence starts at; the at most two partial blocks of a sequence are written
+ * token by token.  Kernel: vllmini_amd/csrc/pa_cache_chunk.hpp.
+ *
+ *   key, value     [num_tokens, num_kv_heads, head_size] fp16, row strides key_stride / value_stride: 16-byte aligned,
+ *                  strides multiples of 8 halves (else VMI_E_ALIGNMENT)
+ *   max_q_len      upper bound on the q_len of any sequence (sizes the grid; the lengths themselves stay on the device)
+ *   num_blocks     key_cache.size(0): a table entry < 0 or >= num_blocks skips that block
+ *   x              key_cache.size(4): 8 (_f16) / 16 (_fp8), else VMI_E_X
+ *   kv_scale       finite and positive, else VMI_E_SHAPE
+ * A sequence with q_len <= 0, seq_lens[s] < q_len, rows outside [0, num_tokens] or more blocks than max_num_blocks_per_seq
+ * writes nothing (the attention's own conditions).  Supported: head_size in {64, 128}, block_size 16.
+ * num_tokens == 0, num_seqs == 0 or max_q_len == 0: returns 0 without a HIP call.
+ */
+int vmi_reshape_and_cache_chunks_f16(
+    const void* key, const void* value, void* key_cache, void* value_cache,
+    int32_t num_tokens, int32_t num_kv_heads, int32_t head_size,
+    const int32_t* block_tables, const int32_t* seq_lens, const int32_t* cu_q_lens,
+    int32_t num_seqs, int32_t max_q_len, int32_t block_size, int32_t x, int32_t max_num_blocks_per_seq, int32_t num_blocks,
+    int64_t key_stride, int64_t value_stride, int64_t kv_block_stride, int64_t kv_head_stride, int32_t device, void* stream);
+int vmi_reshape_and_cache_chunks_fp8(
+    const void* key, const void* value, void* key_cache, void* value_cache,
+    int32_t num_tokens, int32_t num_kv_heads, int32_t head_size,
+    const int32_t* block_tables, const int32_t* seq_lens, const int32_t* cu_q_lens,
+    int32_t num_seqs, int32_t max_q_len, int32_t block_size, int32_t x, int32_t max_num_blocks_per_seq, int32_t num_blocks,
+    int64_t key_stride, int64_t value_stride, int64_t kv_block_stride, int64_t kv_head_stride, int32_t device, void* stream,
+    float kv_scale);
+
+/*
  * The pool's preemption move (extension; counterpart of BlockManager.swap_to_cpu / swap_from_cpu,
  * vllmini/block_manager.py:70-87, which the reference runs as one copy per block, cache_kernels.cu:56-62): ONE launch on
  * `stream` moves block_mapping[i] = (src block, dst block) of BOTH caches for every i.

@@ -9,7 +9,10 @@ GPT-2 small, prompts U{4..512}; warm-up, then a host clock around a synchronise 
                                                      resolved to): run it under
                                                      `rocprofv3 --kernel-trace --stats -- python scripts/prefill_probe.py --trace tiled`
                                                      and read the attention kernel's time; prints the launch's operations
-                                                     (4 D sum(p + 1) per head) and unique K / V bytes per layer beside it."""
+                                                     (4 D sum(p + 1) per head) and unique K / V bytes per layer beside it.
+  prefill_probe.py --cache-write ab                  the tiled path with the cache write by slots (reshape_and_cache) against by
+                                                     chunks (reshape_and_cache_chunks), alternated the same way; with --trace,
+                                                     --cache-write slots | chunks picks the traced call's cache write."""
 import argparse, json, os, sys, time
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -22,6 +25,7 @@ ap.add_argument("--out", default="")
 ap.add_argument("--trace", choices=["positions", "tiled", "auto"], default="")
 ap.add_argument("--n", type=int, default=64)
 ap.add_argument("--kv-cache-dtype", choices=["auto", "fp8"], default="auto")
+ap.add_argument("--cache-write", choices=["slots", "chunks", "ab"], default="slots")
 args = ap.parse_args()
 
 dev = torch.device("cuda:0")
@@ -32,6 +36,10 @@ TILED = "auto" if FP8 else "tiled"              # the third path's name: "tiled"
 PATHS = {"eager": dict(paged_prefill=False), "positions": dict(), TILED: dict(prefill_attention=TILED)}
 if args.trace:
     PATHS.setdefault(args.trace, dict(prefill_attention=args.trace))
+    PATHS[args.trace] = dict(PATHS[args.trace], prefill_cache_write=args.cache_write)
+AB = args.cache_write == "ab"
+if AB:
+    PATHS = {how: dict(prefill_attention=TILED, prefill_cache_write=how) for how in ("slots", "chunks")}
 
 
 def make(n, kw):
@@ -66,7 +74,7 @@ for n in ((args.n,) if args.trace else (1, 8, 32, 64)):
         dec = make(n, PATHS[args.trace])
         for _ in range(4):
             call(dec, n, prompts)
-        print(f"trace {args.trace} -> {dec.prefill_attention} (kv_cache_dtype={args.kv_cache_dtype}): n={n} tokens={tok} layers={dims.n_layer}; per attention launch {flops/1e9:.3f} GFLOP, "
+        print(f"trace {args.trace} -> {dec.prefill_attention}, cache write {dec.prefill_cache_write} (kv_cache_dtype={args.kv_cache_dtype}): n={n} tokens={tok} layers={dims.n_layer}; per attention launch {flops/1e9:.3f} GFLOP, "
               f"unique K/V {kv_bytes/1e6:.2f} MB", flush=True)
         continue
     decs = {name: make(n, kw) for name, kw in PATHS.items()}
@@ -79,6 +87,15 @@ for n in ((args.n,) if args.trace else (1, 8, 32, 64)):
             logits[name] = lg.float().cpu()
     med = {name: float(np.median(v)) for name, v in ts.items()}
     spread = {name: (float(np.min(v)), float(np.max(v))) for name, v in ts.items()}
+    if AB:
+        same = bool(torch.equal(logits["slots"], logits["chunks"]))
+        records.append({"n": n, "tokens": tok, "kv_cache_dtype": args.kv_cache_dtype, "median_ms": {k: v * 1e3 for k, v in med.items()},
+                        "min_max_ms": {k: [a * 1e3, b * 1e3] for k, (a, b) in spread.items()}, "logits_equal": same})
+        print(f"n={n:3d} tokens={tok:6d}  " + "  ".join(f"{k} {med[k]*1e3:8.3f} ms ({spread[k][0]*1e3:.3f} - {spread[k][1]*1e3:.3f})" for k in med) +
+              f"  chunks / slots {med['chunks'] / med['slots']:.3f}  logits equal {same}", flush=True)
+        del decs
+        torch.cuda.empty_cache()
+        continue
     d = {name: (logits[name] - logits["eager"]).abs().max().item() for name in ("positions", TILED)}
     same = (logits[TILED].argmax(-1) == logits["positions"].argmax(-1)).float().mean().item()
     records.append({"n": n, "tokens": tok, "kv_cache_dtype": args.kv_cache_dtype, "median_ms": {k: v * 1e3 for k, v in med.items()},

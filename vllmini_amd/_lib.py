@@ -94,6 +94,13 @@ SIGNATURES = {
     # ... and num_kv_heads
     "vmi_paged_attention_prefill_gqa_plan": (ctypes.c_int, [_i32] * 8 + [ctypes.POINTER(_i32), ctypes.POINTER(_i32),
                                                                      ctypes.POINTER(_i64), _i32]),
+    # the chunk form of the cache write: key, value, key_cache, value_cache, num_tokens, num_kv_heads, head_size, block_tables,
+    # seq_lens, cu_q_lens, num_seqs, max_q_len, block_size, x, max_num_blocks_per_seq, num_blocks, key_stride, value_stride,
+    # kv_block_stride, kv_head_stride, device, stream [, kv_scale]
+    "vmi_reshape_and_cache_chunks_f16": (ctypes.c_int, [_c_void_p] * 4 + [_i32] * 3 + [_c_void_p] * 3 + [_i32] * 6 + [_i64] * 4 +
+                                         [_i32, _c_void_p]),
+    "vmi_reshape_and_cache_chunks_fp8": (ctypes.c_int, [_c_void_p] * 4 + [_i32] * 3 + [_c_void_p] * 3 + [_i32] * 6 + [_i64] * 4 +
+                                         [_i32, _c_void_p, _f32]),
     "vmi_copy_blocks": (ctypes.c_int, [_c_void_p, _c_void_p, _i32, _c_void_p, _i32, _i64, _i32, _c_void_p]),
     "vmi_swap_blocks": (ctypes.c_int, [_c_void_p, _c_void_p, _c_void_p, _i32, _i64, _i32, _i32, _c_void_p]),
     "vmi_swap_blocks_batched": (ctypes.c_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i32, _i64, _i32, _c_void_p]),

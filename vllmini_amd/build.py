@@ -77,7 +77,8 @@ HDR_SPLIT = os.path.join(CSRC, "pa_split.hpp")
 HDR_PREFILL = os.path.join(CSRC, "pa_prefill.hpp")
 HDR_PREFILL_FP8 = os.path.join(CSRC, "pa_prefill_fp8.hpp")
 HDR_PREFILL_SPLIT = os.path.join(CSRC, "pa_prefill_split.hpp")
-HDRS_HOST = [os.path.join(CSRC, "pa_host.hpp"), os.path.join(CSRC, "pa_cache_fp8.hpp")]
+HDRS_HOST = [os.path.join(CSRC, "pa_host.hpp"), os.path.join(CSRC, "pa_cache_fp8.hpp"),
+             os.path.join(CSRC, "pa_cache_chunk.hpp")]       # (the chunk form of the cache write: kernels, launched from pa_prefill.hip)
 INCLUDE = os.path.join(REPO_ROOT, "include")
 OUT_DIR = os.path.join(PKG_DIR, "_C")
 LIB_NAME = "libvmi_paged_attention.so"

@@ -1,6 +1,7 @@
 """`cache_ops` submodule of the reference's extension (paged_attention_cuda.cpp:55-61).
 
   reshape_and_cache   the one op the reference's Python calls (vllmini/model/gpt2.py:81)   -> ops.py
+  reshape_and_cache_chunks  (extension) the same bytes for a prefill chunk, addressed by block table  -> ops.py
   copy_blocks         cache_kernels.cu:96-148    multi-layer block copy (copy-on-write / forking)
   swap_blocks         cache_kernels.cu:24-63     block moves device<->device / device<->host (preemption)
   reshape_and_cache_flash  cache_kernels.cu:283-317  scatter into the flash layout [NB, block_size, H, D]
@@ -17,9 +18,9 @@ from typing import List
 import torch
 
 from . import _lib
-from .ops import _check_device, _raise_native, reshape_and_cache  # noqa: F401
+from .ops import _check_device, _raise_native, reshape_and_cache, reshape_and_cache_chunks  # noqa: F401
 
-__all__ = ["reshape_and_cache", "reshape_and_cache_flash", "swap_blocks", "swap_blocks_batched", "copy_blocks", "convert_fp8"]
+__all__ = ["reshape_and_cache", "reshape_and_cache_chunks", "reshape_and_cache_flash", "swap_blocks", "swap_blocks_batched", "copy_blocks", "convert_fp8"]
 
 
 def copy_blocks(key_caches: List[torch.Tensor], value_caches: List[torch.Tensor],

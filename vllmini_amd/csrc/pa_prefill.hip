@@ -6,6 +6,7 @@
 #include "pa_prefill.hpp"
 #include "pa_prefill_fp8.hpp"
 #include "pa_prefill_split.hpp"
+#include "pa_cache_chunk.hpp"   // the chunk form of the cache write: its launcher and entries are at the end of this file
 
 #include <limits.h>
 
@@ -614,4 +615,110 @@ extern "C" int vmi_paged_attention_prefill_rel_plan(
   }
   return vmi::split_plan(num_tokens, num_heads, head_size, num_seqs, max_q_len, max_seq_len, num_cus, partition_tokens_in,
                          partition_tokens, num_partitions, workspace_bytes, g_shift, sliding_window);
+}
+
+// ----------------------------------------------------------------------------------------
+// The chunk form of the cache write (kernels: pa_cache_chunk.hpp): a prefill chunk's K / V rows into the pages, split by
+// (sequence, cache block, KV head) from the arguments the attention above takes.  The grid is sized from the host's bounds;
+// the lengths stay on the device.
+// ----------------------------------------------------------------------------------------
+namespace vmi {
+
+static int launch_cache_chunks(const void* key, const void* value, void* key_cache, void* value_cache, int32_t num_tokens,
+                               int32_t num_kv_heads, int32_t head_size, const int32_t* block_tables, const int32_t* seq_lens,
+                               const int32_t* cu_q_lens, int32_t num_seqs, int32_t max_q_len, int32_t block_size, int32_t x,
+                               int32_t max_num_blocks_per_seq, int32_t num_blocks, int64_t key_stride, int64_t value_stride,
+                               int64_t kv_block_stride, int64_t kv_head_stride, int32_t device, void* stream, bool fp8,
+                               float kv_scale) {
+  const bool empty = num_tokens == 0 || num_seqs == 0;   // (torch hands out null data pointers for empty tensors)
+  if (!key_cache || !value_cache || (!empty && (!key || !value || !block_tables || !seq_lens || !cu_q_lens)))
+    return fail(VMI_E_NULL_POINTER, "reshape_and_cache_chunks: NULL tensor pointer");
+  if (head_size != 64 && head_size != 128)
+    return fail(VMI_E_HEAD_SIZE, "Unsupported head size: %d (reshape_and_cache_chunks is built for 64 and 128)", head_size);
+  if (block_size != chunkwrite::BS)
+    return fail(VMI_E_BLOCK_SIZE, "Unsupported block size: %d (reshape_and_cache_chunks is built for 16)", block_size);
+  if (x != (fp8 ? 16 : 8))
+    return fail(VMI_E_X, "reshape_and_cache_chunks: key_cache.size(4) must be %d, got %d", fp8 ? 16 : 8, x);
+  if (num_tokens < 0 || num_seqs < 0 || num_kv_heads <= 0 || max_q_len < 0 || max_num_blocks_per_seq < 0 || num_blocks < 0 ||
+      key_stride < 0 || value_stride < 0 || kv_block_stride < 0 || kv_head_stride < 0)
+    return fail(VMI_E_SHAPE, "reshape_and_cache_chunks: negative size (num_tokens=%d num_seqs=%d num_kv_heads=%d max_q_len=%d "
+                "max_num_blocks_per_seq=%d num_blocks=%d)", num_tokens, num_seqs, num_kv_heads, max_q_len,
+                max_num_blocks_per_seq, num_blocks);
+  if (fp8 && !(kv_scale > 0.f && kv_scale <= 3.4028234664e38f))   // (NaN fails the first comparison)
+    return fail(VMI_E_SHAPE, "reshape_and_cache_chunks: kv_scale must be finite and positive, got %g", (double)kv_scale);
+  const int64_t kv_mask = fp8 ? 15 : 7;   // 16 bytes in cache elements
+  if (!aligned16(key) || !aligned16(value) || !aligned16(key_cache) || !aligned16(value_cache) || (key_stride & 7) ||
+      (value_stride & 7) || (kv_block_stride & kv_mask) || (kv_head_stride & kv_mask) ||
+      ((reinterpret_cast<uintptr_t>(block_tables) | reinterpret_cast<uintptr_t>(seq_lens) | reinterpret_cast<uintptr_t>(cu_q_lens)) & 3u))
+    return fail(VMI_E_ALIGNMENT, "reshape_and_cache_chunks: key/value/key_cache/value_cache and their strides must be 16-byte "
+                "aligned (key_stride=%lld value_stride=%lld kv_block_stride=%lld kv_head_stride=%lld)", (long long)key_stride,
+                (long long)value_stride, (long long)kv_block_stride, (long long)kv_head_stride);
+  if (empty || max_q_len == 0) return VMI_OK;
+  // a chunk of q rows that starts at offset 15 of a block touches (q + 30) / 16 blocks; one wave per (sequence, block, KV head)
+  const int64_t nb = ((int64_t)max_q_len + 2 * chunkwrite::BS - 2) / chunkwrite::BS;
+  const int64_t wgs = (nb * num_seqs * num_kv_heads + chunkwrite::WAVES - 1) / chunkwrite::WAVES;
+  if (wgs >= (1ll << 31)) return fail(VMI_E_SHAPE, "reshape_and_cache_chunks: %lld workgroups exceed the grid", (long long)wgs);
+
+  chunkwrite::Params p;
+  p.key = static_cast<const h16*>(key);
+  p.value = static_cast<const h16*>(value);
+  p.kc = key_cache;
+  p.vc = value_cache;
+  p.block_tables = block_tables;
+  p.seq_lens = seq_lens;
+  p.cu_q_lens = cu_q_lens;
+  p.key_stride = key_stride;
+  p.value_stride = value_stride;
+  p.kv_block_stride = kv_block_stride;
+  p.kv_head_stride = kv_head_stride;
+  p.num_tokens = num_tokens;
+  p.num_kv_heads = num_kv_heads;
+  p.num_seqs = num_seqs;
+  p.max_blocks_per_seq = max_num_blocks_per_seq;
+  p.num_blocks = num_blocks;
+  p.nb = (int32_t)nb;
+  p.kv_scale = kv_scale;
+
+  DeviceGuard guard(device);
+  if (guard.err != hipSuccess) return hip_fail(guard.err, "reshape_and_cache_chunks: hipSetDevice");
+  const dim3 grid((unsigned)wgs), block(chunkwrite::WAVES * 64);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (fp8) {
+    if (head_size == 64)
+      hipLaunchKernelGGL((chunkwrite::pa_cache_chunks_kernel<64, true>), grid, block, 0, st, p);
+    else
+      hipLaunchKernelGGL((chunkwrite::pa_cache_chunks_kernel<128, true>), grid, block, 0, st, p);
+  } else if (head_size == 64) {
+    hipLaunchKernelGGL((chunkwrite::pa_cache_chunks_kernel<64, false>), grid, block, 0, st, p);
+  } else {
+    hipLaunchKernelGGL((chunkwrite::pa_cache_chunks_kernel<128, false>), grid, block, 0, st, p);
+  }
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(e, "reshape_and_cache_chunks launch");
+  return VMI_OK;
+}
+
+}  // namespace vmi
+
+extern "C" int vmi_reshape_and_cache_chunks_f16(
+    const void* key, const void* value, void* key_cache, void* value_cache,
+    int32_t num_tokens, int32_t num_kv_heads, int32_t head_size,
+    const int32_t* block_tables, const int32_t* seq_lens, const int32_t* cu_q_lens,
+    int32_t num_seqs, int32_t max_q_len, int32_t block_size, int32_t x, int32_t max_num_blocks_per_seq, int32_t num_blocks,
+    int64_t key_stride, int64_t value_stride, int64_t kv_block_stride, int64_t kv_head_stride, int32_t device, void* stream) {
+  return vmi::launch_cache_chunks(key, value, key_cache, value_cache, num_tokens, num_kv_heads, head_size, block_tables, seq_lens,
+                                  cu_q_lens, num_seqs, max_q_len, block_size, x, max_num_blocks_per_seq, num_blocks, key_stride,
+                                  value_stride, kv_block_stride, kv_head_stride, device, stream, false, 1.0f);
+}
+
+extern "C" int vmi_reshape_and_cache_chunks_fp8(
+    const void* key, const void* value, void* key_cache, void* value_cache,
+    int32_t num_tokens, int32_t num_kv_heads, int32_t head_size,
+    const int32_t* block_tables, const int32_t* seq_lens, const int32_t* cu_q_lens,
+    int32_t num_seqs, int32_t max_q_len, int32_t block_size, int32_t x, int32_t max_num_blocks_per_seq, int32_t num_blocks,
+    int64_t key_stride, int64_t value_stride, int64_t kv_block_stride, int64_t kv_head_stride, int32_t device, void* stream,
+    float kv_scale) {
+  return vmi::launch_cache_chunks(key, value, key_cache, value_cache, num_tokens, num_kv_heads, head_size, block_tables, seq_lens,
+                                  cu_q_lens, num_seqs, max_q_len, block_size, x, max_num_blocks_per_seq, num_blocks, key_stride,
+                                  value_stride, kv_block_stride, kv_head_stride, device, stream, true, kv_scale);
 }

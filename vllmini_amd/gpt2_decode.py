@@ -89,7 +89,8 @@ class GPT2PagedDecoder:
     def __init__(self, dims: GPT2Dims, state_dict: Dict[str, torch.Tensor], pool: PagedKVPool,
                  reference_off_by_one: bool = False, fused_append: bool = False, native_layers: Optional[bool] = None,
                  scatter_in_c_attn: Optional[bool] = None, deferred_scatter: bool = False, pad_batch_to: int = 0,
-                 paged_prefill: Optional[bool] = None, prefill_attention: str = "positions"):
+                 paged_prefill: Optional[bool] = None, prefill_attention: str = "positions",
+                 prefill_cache_write: str = "slots"):
         assert pool.num_layers == dims.n_layer and pool.num_heads == dims.n_head
         assert pool.head_size == dims.head_size
         self.dims, self.sd, self.pool = dims, state_dict, pool
@@ -176,6 +177,22 @@ class GPT2PagedDecoder:
             raise ValueError("prefill_attention='tiled' is built for float16 weights and pages, head size 64 / 128 and block size 16; "
                              f"got {wdt}, kv_cache_dtype='{pool.kv_cache_dtype}', head size {dims.head_size}, block size {pool.block_size}")
         self.prefill_attention = prefill_attention
+        # prefill_cache_write: how prefill_batch puts the prompts' K / V rows into the pages.  "slots" = one reshape_and_cache per
+        # layer over the concatenated slots (today's behaviour).  "chunks" = ops.reshape_and_cache_chunks with the per-sequence
+        # tables, lengths and row offsets the tiled attention takes: whole blocks go out as contiguous tiles whatever packed row
+        # a prompt starts at; same bytes (profiles/prefill_cache_write.md).  It is built for what the tiled kernels serve —
+        # float16 weights, block size 16, head size 64 / 128 — over float16 or fp8-E4M3 pages; anything else raises.
+        # "auto" = "chunks" wherever prefill_attention resolved to "tiled", else "slots"; the attribute holds what it resolved to.
+        if prefill_cache_write not in ("slots", "chunks", "auto"):
+            raise ValueError(f"prefill_cache_write must be 'slots', 'chunks' or 'auto', got {prefill_cache_write!r}")
+        if prefill_cache_write == "auto":
+            prefill_cache_write = "chunks" if prefill_attention == "tiled" else "slots"
+        elif prefill_cache_write == "chunks" and (wdt != torch.float16 or pool.block_size != 16 or dims.head_size not in (64, 128) or
+                                                  pool.kv_cache_dtype not in ("auto", "fp8", "fp8_e4m3")):
+            raise ValueError("prefill_cache_write='chunks' is built for float16 weights, float16 or fp8-E4M3 pages, head size 64 / 128 "
+                             f"and block size 16; got {wdt}, kv_cache_dtype='{pool.kv_cache_dtype}', head size {dims.head_size}, "
+                             f"block size {pool.block_size}")
+        self.prefill_cache_write = prefill_cache_write
         self.pad_batch_to = int(pad_batch_to)      # decode steps are laid out for the next multiple of this many rows (0: as they come)
 
     # ---- pieces shared by prefill and decode --------------------------------------------------------
@@ -249,14 +266,16 @@ class GPT2PagedDecoder:
             for sid in done:       # all or nothing: the caller retries with a smaller group
                 pool.free(sid)
             raise
-        slots_dev = torch.from_numpy(np.ascontiguousarray(np.concatenate(slots, axis=1))).to(dev)     # [layers, sum T]
+        chunks = self.prefill_cache_write == "chunks"      # the rows go in by (sequence, block): no slots on the device
+        if not chunks:
+            slots_dev = torch.from_numpy(np.ascontiguousarray(np.concatenate(slots, axis=1))).to(dev)     # [layers, sum T]
         ids = torch.as_tensor([t for p in prompts for t in p], dtype=torch.long, device=dev)
         starts = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
         pos = torch.from_numpy(np.concatenate([np.arange(T, dtype=np.int64) for T in lens])).to(dev)
         x = self.sd["transformer.wte.weight"][ids] + self.sd["transformer.wpe.weight"][pos]
         tiled = self.prefill_attention == "tiled"
         paged = self.paged_prefill and not tiled
-        if tiled:
+        if tiled or chunks:
             mbe = -(-max(lens) // pool.block_size)
             tables_seq = torch.from_numpy(np.ascontiguousarray(np.stack(tabs, axis=1)[:, :, :mbe])).to(dev)   # [layers, n, mbe]
             lens_seq = torch.as_tensor(lens, dtype=torch.int32).to(dev)
@@ -292,7 +311,11 @@ class GPT2PagedDecoder:
         for i in range(d.n_layer):
             p = f"transformer.h.{i}."
             q, k, v = self._qkv(self._ln(x, p + "ln_1"), p)                                       # [sum T, H, D] views
-            cache_ops.reshape_and_cache(k, v, pool.key_cache, pool.value_cache, slots_dev[i], pool.kv_cache_dtype, pool.kv_scale)
+            if chunks:
+                cache_ops.reshape_and_cache_chunks(k, v, pool.key_cache, pool.value_cache, tables_seq[i], lens_seq, cu_q, max(lens),
+                                                   pool.kv_cache_dtype, pool.kv_scale)
+            else:
+                cache_ops.reshape_and_cache(k, v, pool.key_cache, pool.value_cache, slots_dev[i], pool.kv_cache_dtype, pool.kv_scale)
             a = torch.empty((x.shape[0], E), dtype=x.dtype, device=dev)
             if tiled:
                 ops.paged_attention_prefill(a.view(-1, H, D), q, pool.key_cache, pool.value_cache, H, self.scale, tables_seq[i],

@@ -34,6 +34,7 @@ __all__ = [
     "paged_attention_v2",
     "paged_attention_prefill",
     "reshape_and_cache",
+    "reshape_and_cache_chunks",
     "pick_variant",
     "workspace_for",
     "prefill_workspace_for",
@@ -923,6 +924,96 @@ def reshape_and_cache(
         slot_mapping.data_ptr(), num_tokens, num_heads, head_size, block_size, x,
         kst[0], vst[0],                                                   # cache_kernels.cu:271-272
         index, stream)
+    if rc != 0:
+        _raise_native(rc)
+    return None
+
+
+def reshape_and_cache_chunks(
+    key: torch.Tensor,
+    value: torch.Tensor,
+    key_cache: torch.Tensor,
+    value_cache: torch.Tensor,
+    block_tables: torch.Tensor,
+    seq_lens: torch.Tensor,
+    cu_q_lens: torch.Tensor,
+    max_q_len: int,
+    kv_cache_dtype: str = "auto",
+    kv_scale: float = 1.0,
+) -> None:
+    """The cache write of a prefill chunk, addressed like paged_attention_prefill instead of by slot (extension); in place,
+    returns None.
+
+    key / value [num_tokens, num_kv_heads, head_size] float16 (rows may be strided: the fused projection's views); sequence s
+    owns rows cu_q_lens[s] .. cu_q_lens[s+1]-1, which go to positions seq_lens[s] - q_len .. seq_lens[s] - 1 of the blocks in
+    block_tables[s] — the bytes reshape_and_cache writes for the slots table[pos // 16] * 16 + pos % 16, bit for bit, and no
+    other byte.  `max_q_len` bounds the q_len of every sequence (host-known: it sizes the grid).  One wave per (sequence, cache
+    block, KV head) writes a whole block as contiguous tiles whatever packed row the sequence starts at (csrc/pa_cache_chunk.hpp;
+    profiles/prefill_cache_write.md).  Built for float16 rows, head size 64 / 128, block size 16, pages float16 ("auto", x = 8)
+    or fp8-E4M3 ("fp8" / "fp8_e4m3", x = 16); anything else raises RuntimeError — there is no fallback to the slot operator.
+    A sequence whose lengths the tensors cannot hold writes nothing; a table entry outside the pool skips its block."""
+    fp8 = _check_kv_cache_dtype(kv_cache_dtype)
+    if fp8 == 2:
+        raise RuntimeError(f"reshape_and_cache_chunks is not built for E5M2 pages (kv_cache_dtype='{kv_cache_dtype}'); "
+                           "float16 ('auto') and fp8-E4M3 ('fp8', 'fp8_e4m3') pages are")
+    x = 16 if fp8 else 8
+    kshape = key.shape
+    if len(kshape) != 3 or kshape != value.shape:
+        raise RuntimeError("key and value must both be [num_tokens, num_kv_heads, head_size]")
+    if key.dtype != torch.float16 or value.dtype != torch.float16:
+        raise RuntimeError(f"Unsupported input type of reshape_and_cache_chunks: {key.dtype} (float16 is built)")
+    num_tokens, num_kv_heads, head_size = kshape
+    ks, vs = key_cache.shape, value_cache.shape
+    if len(ks) != 5 or len(vs) != 4:
+        raise RuntimeError("key_cache must be [num_blocks, num_kv_heads, head_size/x, block_size, x] "
+                           "and value_cache [num_blocks, num_kv_heads, head_size, block_size]")
+    if head_size not in (64, 128):
+        raise RuntimeError(f"Unsupported head size: {head_size} (reshape_and_cache_chunks is built for 64 and 128)")
+    if ks[3] != 16 or vs[3] != 16:
+        raise RuntimeError(f"Unsupported block size: {ks[3]} (reshape_and_cache_chunks is built for 16)")
+    if ks[4] != x:
+        raise RuntimeError(f"key_cache innermost dimension must be {x} (16 bytes per chunk), got {ks[4]}")
+    index = key.get_device()
+    dev = key.device
+    if index < 0:
+        _check_device("key", key, dev)
+    _on("value", value, index, dev)
+    _on("key_cache", key_cache, index, dev)
+    _on("value_cache", value_cache, index, dev)
+    _on("block_tables", block_tables, index, dev)
+    _on("seq_lens", seq_lens, index, dev)
+    _on("cu_q_lens", cu_q_lens, index, dev)
+    if fp8:
+        _check_fp8_cache_dtype(fp8, key_cache, value_cache, kv_cache_dtype)
+    elif key_cache.dtype != torch.float16 or value_cache.dtype != torch.float16:
+        raise RuntimeError("key_cache/value_cache must be torch.float16 for kv_cache_dtype='auto' (fp8-E4M3 pages: kv_cache_dtype='fp8')")
+    if block_tables.dtype != torch.int32 or seq_lens.dtype != torch.int32 or cu_q_lens.dtype != torch.int32:
+        raise RuntimeError("block_tables, seq_lens and cu_q_lens must be int32")
+    if ks[0] != vs[0] or ks[1] != num_kv_heads or vs[1] != num_kv_heads or ks[2] * x != head_size or vs[2] != head_size:
+        raise RuntimeError("cache shapes do not match key/value shapes")
+    kst, vst = key.stride(), value.stride()
+    if kst[2] != 1 or kst[1] != head_size or vst[2] != 1 or vst[1] != head_size:
+        raise RuntimeError("key/value must be contiguous in their last two dimensions")
+    kcs, vcs = key_cache.stride(), value_cache.stride()
+    tile = head_size * 16
+    if kcs[4] != 1 or kcs[3] != x or kcs[2] != 16 * x or (kcs[1] != tile and ks[1] != 1) or vcs[3] != 1 or vcs[2] != 16 or \
+            (vcs[1] != tile and vs[1] != 1):
+        raise RuntimeError("each cache block must be dense")
+    if vcs[0] != kcs[0] or vcs[1] != kcs[1]:
+        raise RuntimeError("key_cache and value_cache must have identical block/head strides")
+    ts, tst = block_tables.shape, block_tables.stride()
+    num_seqs = seq_lens.shape[0] if seq_lens.dim() == 1 else -1
+    if num_seqs < 0 or not seq_lens.is_contiguous():
+        raise RuntimeError("seq_lens must be a contiguous [num_seqs] tensor")
+    if len(ts) != 2 or ts[0] != num_seqs or tst[1] != 1 or (tst[0] != ts[1] and num_seqs > 1):
+        raise RuntimeError("block_tables must be a row-contiguous [num_seqs, max_num_blocks_per_seq] tensor")
+    if cu_q_lens.dim() != 1 or cu_q_lens.shape[0] != num_seqs + 1 or not cu_q_lens.is_contiguous():
+        raise RuntimeError("cu_q_lens must be a contiguous [num_seqs + 1] tensor")
+    args = (key.data_ptr(), value.data_ptr(), key_cache.data_ptr(), value_cache.data_ptr(), num_tokens, num_kv_heads, head_size,
+            block_tables.data_ptr(), seq_lens.data_ptr(), cu_q_lens.data_ptr(), num_seqs, int(max_q_len), 16, x, ts[1], ks[0],
+            kst[0], vst[0], kcs[0], kcs[1], index, _stream_of(index))
+    lib = _lib.load()
+    rc = lib.vmi_reshape_and_cache_chunks_fp8(*args, float(kv_scale)) if fp8 else lib.vmi_reshape_and_cache_chunks_f16(*args)
     if rc != 0:
         _raise_native(rc)
     return None
