@@ -630,6 +630,43 @@ int vmi_paged_attention_prefill_rel_plan(
     int64_t* workspace_bytes, int32_t num_kv_heads, int32_t sliding_window, int32_t form);
 
 /*
+ * The same operator with a TOKEN TREE as the chunk (added under ABI 22 like the entries above): the verification rows of a
+ * speculative decoder whose candidates branch (SpecInfer, Medusa, EAGLE), in one chunk instead of one sequence per root-to-leaf
+ * path.  tree_mask holds one 64-bit word per packed query row, read as unsigned.  With row r = row j of sequence s's chunk and
+ * ctx = seq_lens[s] - q_len, row r attends every cached token t < ctx and chunk token ctx + i, i <= j, iff bit i of tree_mask[r] is
+ * set.  Bit j (the row itself) always counts as set; bits above j are ignored — nodes come in a topological order, ancestors in
+ * front of descendants — so all ones is plain causal attention for that row.  Row j's K / V sit at cached position ctx + j, in
+ * the cache before the call like every other row of the chunk.  Kernels: the TREE form in vllmini_amd/csrc/pa_prefill.hpp /
+ * pa_prefill_fp8.hpp (pa_prefill_tree_kernel / pa_prefill_tree_fp8_kernel); the entries above launch what they launched before.
+ * Arguments and validation are vmi_paged_attention_prefill_split_f16's / _fp8's — grid, partitions and workspace too: plan with
+ * vmi_paged_attention_prefill_split_plan, form 2 with vmi_paged_attention_prefill_gqa_plan; one partition is valid with a NULL
+ * workspace — and in addition:
+ *   tree_mask        device pointer to num_tokens 64-bit words; NULL: VMI_E_NULL_POINTER; not 8-byte aligned: VMI_E_ALIGNMENT
+ *   max_q_len        at most 64 (the bits of a word), else VMI_E_SHAPE; a sequence whose q_len on the device exceeds 64 writes
+ *                    nothing, like the other malformed lengths
+ *   form             0: the plain tiles, 1: the cooperative ones, 2: the head-packed ones (num_heads / num_kv_heads in {2, 4, 8, 16},
+ *                    else VMI_E_KV_HEADS); anything else VMI_E_SHAPE.
+ * Fixed orders, no atomics: run-to-run bit-identical, and with all-ones words bit-identical to the entry of the same form above.
+ * A tree together with a shared prefix, ALiBi slopes or a sliding window is not built.
+ */
+int vmi_paged_attention_prefill_tree_f16(
+    void* out, const void* query, const void* key_cache, const void* value_cache,
+    int32_t num_tokens, int32_t num_heads, int32_t head_size, int32_t num_kv_heads, float scale,
+    const int32_t* block_tables, const int32_t* seq_lens, const int32_t* cu_q_lens,
+    int32_t num_seqs, int32_t max_q_len, int32_t block_size, int32_t max_num_blocks_per_seq,
+    int64_t q_stride, int64_t kv_block_stride, int64_t kv_head_stride, int32_t device, void* stream,
+    int32_t max_seq_len, int32_t partition_tokens, void* workspace, int64_t workspace_bytes,
+    const uint64_t* tree_mask, int32_t form);
+int vmi_paged_attention_prefill_tree_fp8(
+    void* out, const void* query, const void* key_cache, const void* value_cache,
+    int32_t num_tokens, int32_t num_heads, int32_t head_size, int32_t num_kv_heads, float scale,
+    const int32_t* block_tables, const int32_t* seq_lens, const int32_t* cu_q_lens,
+    int32_t num_seqs, int32_t max_q_len, int32_t block_size, int32_t max_num_blocks_per_seq,
+    int64_t q_stride, int64_t kv_block_stride, int64_t kv_head_stride, int32_t device, void* stream,
+    int32_t max_seq_len, int32_t partition_tokens, void* workspace, int64_t workspace_bytes, float kv_scale,
+    const uint64_t* tree_mask, int32_t form);
+
+/*
  * The cache write of a prefill CHUNK (extension; added under ABI 22 like the entries above): the bytes of
  * vmi_reshape_and_cache_f16 / _fp8, addressed the way the tiled attention addresses them instead of by slot.  Sequence s owns
  * rows cu_q_lens[s] .. cu_q_lens[s+1]-1 of key / value; row j sits at position pos = seq_lens[s] - q_len + j and goes to offset

@@ -88,6 +88,9 @@ SIGNATURES = {
     # ... its plan: the split plan's arguments and results, then num_kv_heads, sliding_window, form
     "vmi_paged_attention_prefill_rel_plan": (ctypes.c_int, [_i32] * 8 + [ctypes.POINTER(_i32), ctypes.POINTER(_i32),
                                                                      ctypes.POINTER(_i64), _i32, _i32, _i32]),
+    # the TREE form (a token tree as the chunk): the split entries' arguments plus tree_mask, form
+    "vmi_paged_attention_prefill_tree_f16": (ctypes.c_int, list(_PREFILL_ARGS) + [_i32, _i32, _c_void_p, _i64, _c_void_p, _i32]),
+    "vmi_paged_attention_prefill_tree_fp8": (ctypes.c_int, list(_PREFILL_ARGS) + [_i32, _i32, _c_void_p, _i64, _f32, _c_void_p, _i32]),
     # num_tokens, num_heads, head_size, num_seqs, max_q_len, max_seq_len, num_cus, partition_tokens_in, -> 3 results
     "vmi_paged_attention_prefill_split_plan": (ctypes.c_int, [_i32] * 8 + [ctypes.POINTER(_i32), ctypes.POINTER(_i32),
                                                                        ctypes.POINTER(_i64)]),

@@ -149,6 +149,31 @@ static void launch_rel(const P& p, int head_size, bool coop, dim3 grid, dim3 blo
   else
     launch_rel_form<SPLIT, false, false>(p, head_size, grid, block, st);
 }
+// the TREE kernels (a token tree as the chunk): twenty-four instantiations again — two page formats x two head sizes x the plain,
+// SPLIT, COOP, SPLIT + COOP, PACK and PACK + SPLIT forms
+template <bool SPLIT, bool COOP, bool PACK>
+static void launch_tree_form(const prefill::TreeParams& p, int head_size, dim3 grid, dim3 block, hipStream_t st) {
+  if (head_size == 64)
+    hipLaunchKernelGGL((prefill::pa_prefill_tree_kernel<64, SPLIT, COOP, PACK>), grid, block, 0, st, p);
+  else
+    hipLaunchKernelGGL((prefill::pa_prefill_tree_kernel<128, SPLIT, COOP, PACK>), grid, block, 0, st, p);
+}
+template <bool SPLIT, bool COOP, bool PACK>
+static void launch_tree_form(const prefill::TreeParamsFp8& p, int head_size, dim3 grid, dim3 block, hipStream_t st) {
+  if (head_size == 64)
+    hipLaunchKernelGGL((prefill::pa_prefill_tree_fp8_kernel<64, SPLIT, COOP, PACK>), grid, block, 0, st, p);
+  else
+    hipLaunchKernelGGL((prefill::pa_prefill_tree_fp8_kernel<128, SPLIT, COOP, PACK>), grid, block, 0, st, p);
+}
+template <bool SPLIT, class P>
+static void launch_tree(const P& p, int head_size, bool coop, dim3 grid, dim3 block, hipStream_t st) {
+  if (p.g_shift >= 0)
+    launch_tree_form<SPLIT, true, true>(p, head_size, grid, block, st);
+  else if (coop)
+    launch_tree_form<SPLIT, true, false>(p, head_size, grid, block, st);
+  else
+    launch_tree_form<SPLIT, false, false>(p, head_size, grid, block, st);
+}
 template <bool SPLIT, class P>
 static void launch_tiles(const P& p, int head_size, bool coop, dim3 grid, dim3 block, hipStream_t st) {
   if (p.g_shift >= 0)
@@ -167,6 +192,8 @@ static void launch_tiles(const P& p, int head_size, bool coop, dim3 grid, dim3 b
 // form of the SUFFIX launch, whose partition axis starts at part0 = 1; the merge launch is the same.
 // rel (the REL entries, which checked window >= 0): the REL kernels of the same form with alibi_slopes (may be NULL) and window
 // (0: none); the plan counts on min(max_seq_len, window + max_q_len - 1), and the merge is the REL one.
+// tree_mask (the TREE entries, which checked it and max_q_len <= 64; never with prefix or rel): the TREE kernels of the same form
+// on the same grid, plan and workspace; the merge is the same kernel under the TREE guard (MergeTreeParams).
 static int launch_pa_prefill(void* out, const void* query, const void* key_cache, const void* value_cache,
                              int32_t num_tokens, int32_t num_heads, int32_t head_size, int32_t num_kv_heads, float scale,
                              const int32_t* block_tables, const int32_t* seq_lens, const int32_t* cu_q_lens,
@@ -175,7 +202,7 @@ static int launch_pa_prefill(void* out, const void* query, const void* key_cache
                              void* stream, bool fp8, float kv_scale, int32_t max_seq_len = -1,
                              int32_t partition_tokens = 0, void* workspace = nullptr, int64_t workspace_bytes = 0,
                              bool coop = false, bool pack = false, int32_t prefix = 0, bool rel = false,
-                             const float* alibi_slopes = nullptr, int32_t window = 0) {
+                             const float* alibi_slopes = nullptr, int32_t window = 0, const uint64_t* tree_mask = nullptr) {
   // one validation for both page formats; the cache strides are in cache elements: halves, or bytes when fp8
   const bool empty = num_tokens == 0 || num_seqs == 0;   // (torch hands out null data pointers for empty tensors)
   if (!key_cache || !value_cache || (!empty && (!out || !query || !block_tables || !seq_lens || !cu_q_lens)))
@@ -281,6 +308,23 @@ static int launch_pa_prefill(void* out, const void* query, const void* key_cache
       go(p, scale);
     }
   };
+  // the TREE kernels of either page format, split or not: the same fields plus the words
+  auto tree_tiles = [&](auto split) {
+    auto go = [&](auto& p, float score_scale) {
+      fill(p);
+      p.scale_log2e = score_scale * 1.4426950408889634f;
+      p.tree_mask = tree_mask;
+      launch_tree<decltype(split)::value>(p, head_size, coop, grid, block, st);
+    };
+    if (fp8) {
+      prefill::TreeParamsFp8 p;
+      p.kv_scale = kv_scale;
+      go(p, scale * kv_scale);
+    } else {
+      prefill::TreeParams p;
+      go(p, scale);
+    }
+  };
   if (parts > 1) {
     // partition kernels, then the merge, on the caller's stream: the second launch is the only synchronisation
     prefill::MergeParams mp;
@@ -298,6 +342,8 @@ static int launch_pa_prefill(void* out, const void* query, const void* key_cache
     mp.out_scale = fp8 ? kv_scale : 1.0f;
     if (rel) {
       rel_tiles(std::true_type());
+    } else if (tree_mask) {
+      tree_tiles(std::true_type());
     } else if (fp8) {
       prefill::ParamsFp8 p;
       fill(p);
@@ -324,6 +370,13 @@ static int launch_pa_prefill(void* out, const void* query, const void* key_cache
         hipLaunchKernelGGL(prefill::pa_prefill_merge_rel_kernel<64>, mgrid, dim3(256), 0, st, mrp);
       else
         hipLaunchKernelGGL(prefill::pa_prefill_merge_rel_kernel<128>, mgrid, dim3(256), 0, st, mrp);
+    } else if (tree_mask) {
+      prefill::MergeTreeParams mtp;
+      static_cast<prefill::MergeParams&>(mtp) = mp;
+      if (head_size == 64)
+        hipLaunchKernelGGL((prefill::pa_prefill_merge_kernel<64, prefill::MergeTreeParams>), mgrid, dim3(256), 0, st, mtp);
+      else
+        hipLaunchKernelGGL((prefill::pa_prefill_merge_kernel<128, prefill::MergeTreeParams>), mgrid, dim3(256), 0, st, mtp);
     } else if (head_size == 64)
       hipLaunchKernelGGL(prefill::pa_prefill_merge_kernel<64>, mgrid, dim3(256), 0, st, mp);
     else
@@ -334,6 +387,8 @@ static int launch_pa_prefill(void* out, const void* query, const void* key_cache
   }
   if (rel) {
     rel_tiles(std::false_type());
+  } else if (tree_mask) {
+    tree_tiles(std::false_type());
   } else if (fp8) {
     prefill::ParamsFp8 p;
     fill(p);
@@ -615,6 +670,56 @@ extern "C" int vmi_paged_attention_prefill_rel_plan(
   }
   return vmi::split_plan(num_tokens, num_heads, head_size, num_seqs, max_q_len, max_seq_len, num_cus, partition_tokens_in,
                          partition_tokens, num_partitions, workspace_bytes, g_shift, sliding_window);
+}
+
+// the TREE entries' own checks, in front of the common ones
+static int check_tree(int32_t num_tokens, int32_t num_seqs, int32_t max_q_len, int32_t max_seq_len, const uint64_t* tree_mask,
+                      int32_t form) {
+  if (max_seq_len < 0) return vmi::fail(VMI_E_SHAPE, "paged_attention_prefill: negative max_seq_len=%d", max_seq_len);
+  if (!tree_mask && num_tokens != 0 && num_seqs != 0)   // (torch hands out null data pointers for empty tensors)
+    return vmi::fail(VMI_E_NULL_POINTER, "paged_attention_prefill: NULL tree_mask");
+  if (reinterpret_cast<uintptr_t>(tree_mask) & 7u)
+    return vmi::fail(VMI_E_ALIGNMENT, "paged_attention_prefill: tree_mask must be 8-byte aligned");
+  if (max_q_len > vmi::prefill::TREE_ROWS)
+    return vmi::fail(VMI_E_SHAPE, "paged_attention_prefill: tree_mask holds one 64-bit word per row: max_q_len must be at most "
+                     "%d, got %d", vmi::prefill::TREE_ROWS, max_q_len);
+  if (form < 0 || form > 2)
+    return vmi::fail(VMI_E_SHAPE, "paged_attention_prefill: form must be 0 (plain), 1 (cooperative) or 2 (head-packed), got %d", form);
+  return VMI_OK;
+}
+
+extern "C" int vmi_paged_attention_prefill_tree_f16(
+    void* out, const void* query, const void* key_cache, const void* value_cache,
+    int32_t num_tokens, int32_t num_heads, int32_t head_size, int32_t num_kv_heads, float scale,
+    const int32_t* block_tables, const int32_t* seq_lens, const int32_t* cu_q_lens,
+    int32_t num_seqs, int32_t max_q_len, int32_t block_size, int32_t max_num_blocks_per_seq,
+    int64_t q_stride, int64_t kv_block_stride, int64_t kv_head_stride, int32_t device, void* stream,
+    int32_t max_seq_len, int32_t partition_tokens, void* workspace, int64_t workspace_bytes,
+    const uint64_t* tree_mask, int32_t form) {
+  const int rc = check_tree(num_tokens, num_seqs, max_q_len, max_seq_len, tree_mask, form);
+  if (rc != VMI_OK) return rc;
+  return vmi::launch_pa_prefill(out, query, key_cache, value_cache, num_tokens, num_heads, head_size, num_kv_heads, scale,
+                                block_tables, seq_lens, cu_q_lens, num_seqs, max_q_len, block_size, max_num_blocks_per_seq,
+                                q_stride, kv_block_stride, kv_head_stride, device, stream, false, 1.0f, max_seq_len,
+                                partition_tokens, workspace, workspace_bytes, form >= 1, form == 2, 0, false, nullptr, 0,
+                                tree_mask);
+}
+
+extern "C" int vmi_paged_attention_prefill_tree_fp8(
+    void* out, const void* query, const void* key_cache, const void* value_cache,
+    int32_t num_tokens, int32_t num_heads, int32_t head_size, int32_t num_kv_heads, float scale,
+    const int32_t* block_tables, const int32_t* seq_lens, const int32_t* cu_q_lens,
+    int32_t num_seqs, int32_t max_q_len, int32_t block_size, int32_t max_num_blocks_per_seq,
+    int64_t q_stride, int64_t kv_block_stride, int64_t kv_head_stride, int32_t device, void* stream,
+    int32_t max_seq_len, int32_t partition_tokens, void* workspace, int64_t workspace_bytes, float kv_scale,
+    const uint64_t* tree_mask, int32_t form) {
+  const int rc = check_tree(num_tokens, num_seqs, max_q_len, max_seq_len, tree_mask, form);
+  if (rc != VMI_OK) return rc;
+  return vmi::launch_pa_prefill(out, query, key_cache, value_cache, num_tokens, num_heads, head_size, num_kv_heads, scale,
+                                block_tables, seq_lens, cu_q_lens, num_seqs, max_q_len, block_size, max_num_blocks_per_seq,
+                                q_stride, kv_block_stride, kv_head_stride, device, stream, true, kv_scale, max_seq_len,
+                                partition_tokens, workspace, workspace_bytes, form >= 1, form == 2, 0, false, nullptr, 0,
+                                tree_mask);
 }
 
 // ----------------------------------------------------------------------------------------

@@ -76,6 +76,14 @@ struct RelParams : Params {
   const float* alibi_slopes;    // [num_heads] fp32, or NULL
   int32_t window;               // W of the sliding window, 0: none
 };
+// The TREE kernels' argument (again a type of its own)
+struct TreeParams : Params {
+  const uint64_t* tree_mask;    // [num_tokens]: one word per packed query row — bit i: the row attends token i of its own chunk
+};
+constexpr int TREE_ROWS = 64;   // a chunk's rows under a tree mask: the bits of a word
+// the longest chunk the kernels of argument type P serve (the TREE types: TREE_ROWS)
+template <class P> inline constexpr int max_chunk_rows = 0x7fffffff;
+template <> inline constexpr int max_chunk_rows<TreeParams> = TREE_ROWS;
 
 // THE guard of every kernel of the operator (unsplit, partition form, merge): a sequence with nothing to do, or with
 // lengths the tensors cannot hold or the host did not plan for, writes nothing.  -> false: leave.
@@ -86,7 +94,7 @@ __device__ __forceinline__ bool seq_span(const P& p, int seq, int& row_lo, int& 
   q_len = row_hi - row_lo;
   L = p.seq_lens[seq];
   return !(q_len <= 0 || L <= 0 || L - q_len < 0 || row_lo < 0 || row_hi > p.num_tokens ||
-           (L + BS - 1) / BS > p.max_blocks_per_seq || L > p.max_seq_len);
+           (L + BS - 1) / BS > p.max_blocks_per_seq || L > p.max_seq_len || q_len > max_chunk_rows<P>);
 }
 
 // The partition form's epilogue: lane (n, kg) stores its column's UNNORMALISED fp32 accumulator — dims 16t + 4kg .. + 3 of
@@ -317,6 +325,47 @@ struct Rel {
   __device__ __forceinline__ int below(int tok0) const { return min(max(lo - tok0, 0), 4); }
 };
 
+// What the TREE form (the kernels' comment below) adds to a column's state, over both page formats.  ctx = the cached tokens in
+// front of the chunk — a tile's columns are rows of ONE sequence, so it is wave-uniform and sits in a scalar register; word =
+// the row's 64 bits, bit i: chunk token ctx + i is attended — bits above the row's own index j = pos - ctx cleared, bit j set,
+// once, here (the guard passed: q_len <= 64, j <= 63).  Columns of one row (PACK: its G heads) and dead columns (which repeat
+// the chunk's last row) read the word at their q_row.
+struct Tree {
+  int ctx;
+  uint64_t word;
+  template <class P>
+  __device__ __forceinline__ void init(const P& p, const Column& c) {
+    ctx = __builtin_amdgcn_readfirstlane(p.seq_lens[c.table_row] - (p.cu_q_lens[c.table_row + 1] - p.cu_q_lens[c.table_row]));
+    const int j = c.pos - ctx;
+    word = (p.tree_mask[c.q_row] & ((2ull << j) - 1ull)) | (1ull << j);   // (j == 63: 2 << 63 wraps to 0, the mask is all ones)
+  }
+  // does pair pp hold a chunk token?  (wave-uniform; the at most three pairs that overlap [ctx, last_pos])
+  __device__ __forceinline__ bool edge(int pp) const { return 32 * pp + 31 >= ctx; }
+  // bit r: token tok0 + r is attended — it lies below ctx, or it is chunk token d + r, d = tok0 - ctx, and that bit of the
+  // word is set.  d <= -4: all four are context; -4 < d < 0: the low -d are; d >= 64: past bit 63, none (bits past the row's own
+  // are clear, so tokens above pos and past the tile's last position drop out with them).  No shift count leaves 0 .. 63.
+  __device__ __forceinline__ uint32_t keep(int tok0) const {
+    const int d = tok0 - ctx;
+    const int up = min(max(-d, 0), 4);
+    const uint64_t w = d >= 64 ? 0ull : d >= 0 ? word >> (d & 63) : (word << up) | ((1ull << up) - 1ull);
+    return (uint32_t)w & 15u;
+  }
+  // the fp32 scores of tokens tok0 .. tok0 + 3: scaled; on an edge pair the SELECTED -inf where the bit is clear (a K row past
+  // the tile's last position may be NaN: nothing of it survives the select); -> their maximum
+  __device__ __forceinline__ float scores(float (&s)[4], const f32x4& acc, float scale, int tok0, bool on_edge) const {
+    float mx = -INFINITY;
+    if (on_edge) {   // (wave-uniform)
+      const uint32_t k = keep(tok0);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) mx = fmaxf(mx, s[r] = (k >> r & 1u) ? acc[r] * scale : -INFINITY);
+    } else {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) mx = fmaxf(mx, s[r] = acc[r] * scale);
+    }
+    return mx;
+  }
+};
+
 // Grid: one workgroup per (64-row group, sequence, head), x = group_rev * (num_seqs * num_heads) + seq * num_heads + head.
 // group_rev counts a sequence's groups from its LAST one, so the first num_seqs * num_heads workgroups of the launch are
 // every sequence's longest causal range; a sequence with fewer groups than the host bound leaves the surplus at once.
@@ -388,11 +437,29 @@ struct Rel {
 // partition wholly below the tile's window, in Rel::bounds — and it depends on (part, the tile's first and last position, W) alone,
 // which the four waves of a cooperating workgroup share; the loop still holds no exit.  A stored column sees at least itself:
 // its maximum contributes exp2(0), sum >= 1.
-template <int D, bool SPLIT, bool COOP, bool PACK, bool PREFIX, bool REL = false, class P = Params>
+//
+// TREE (a token tree as the chunk — the verification rows of a speculative decoder — on the plain, SPLIT, COOP and PACK forms; kernels
+// pa_prefill_tree_kernel, argument TreeParams; never with PREFIX or REL): row j of a chunk attends every cached token t < ctx and
+// chunk token ctx + i, i <= j, iff bit i of its 64-bit word is set; bit j counts as set, bits above j are ignored (nodes come in
+// a topological order: ancestors first).  Chunks of at most 64 rows: the guard (seq_span) rejects a longer one, in the tile kernels
+// and in the merge.  The state is struct Tree, above.  Since no row sees past its own position, last_pos, the walk bounds, the
+// partitions a row owns (0 .. pos / PT), the grid, the workspace and the merge arithmetic are the causal forms'.  MASKS: a pair that
+// ends below ctx holds context tokens only and runs with NO select (Tree::edge, wave-uniform — the causal kernels select on every
+// trip); the at most three pairs that overlap [ctx, last_pos] SELECT -inf where the bit is clear, by one guarded shift per four
+// tokens (Tree::keep).  The clearing of V past last_pos, the double buffer, both MFMAs and the merges are untouched: an
+// unattended chunk token at or below last_pos is a row the caller wrote — finite — and meets p = 0.  EMPTY SHARES: a column may
+// see NO token in a whole trip, wave share or partition (a node without ancestors over ctx = 0: the pairs below its own hold other
+// branches only).  m starts at -3e38, not -inf, so a trip of all -inf keeps m (fmaxf), alpha = exp2(0) = 1, and every
+// p = exp2(-inf - m) = 0: the triple stays (m = -3e38, l = 0, o = 0).  coop_merge and the merge kernel give it the weight
+// exp2(-3e38 - M) = 0 against the share that holds the row itself (M finite, l >= 1) — or exp2(0) on terms that are all 0 — and
+// never form -inf - (-inf).  A row's own partition and the unsplit tile always hold the row itself: sum >= 1.  THE BARRIER RULE is
+// unchanged: TREE adds no return (the longer-chunk exit is the guard's, per sequence: workgroup-uniform).
+template <int D, bool SPLIT, bool COOP, bool PACK, bool PREFIX, bool REL = false, bool TREE = false, class P = Params>
 __device__ __forceinline__ void prefill_tile(const P& p) {
   static_assert(COOP || !PACK, "the head-packed form is cooperative by construction");
   static_assert(!PREFIX || (SPLIT && COOP && !PACK), "the shared-prefix form is a cooperative tile of partition 0, one query head");
   static_assert(!REL || !PREFIX, "ALiBi / sliding window over a shared prefix is not built");
+  static_assert(!TREE || (!PREFIX && !REL), "a token tree with a shared prefix, ALiBi or a sliding window is not built");
   constexpr int KC = D / 32;    // 32-dim chunks of a K block: one MFMA each
   constexpr int VT = D / 16;    // 16-dim tiles of the output: one MFMA each
   const int lane = threadIdx.x & 63;
@@ -419,6 +486,8 @@ __device__ __forceinline__ void prefill_tile(const P& p) {
     pp1 = min(npair, pp0 + (p.part_tokens >> 5));
   }
   const int blk_lo = REL ? rel.lo / BS : 0;                // REL: the first block the tile may read
+  Tree tree;
+  if constexpr (TREE) tree.init(p, col);
 
   const h16* qp = p.q + (int64_t)col.q_row * p.q_stride + (int64_t)head * D + 8 * kg;
   h16x8 qB[KC];
@@ -479,7 +548,7 @@ __device__ __forceinline__ void prefill_tile(const P& p) {
     // ---- S^T = K . Q^T, scaled in fp32, causal mask selected ----
     float s[2][4];
     float mx = -INFINITY;
-    const bool on_edge = REL && rel.edge(pp);                                        // (wave-uniform)
+    const bool on_edge = REL ? rel.edge(pp) : TREE && tree.edge(pp);                 // (wave-uniform)
     const float dist = REL ? (float)(2 * pp * BS + 4 * kg - pos) : 0.f;             // REL: my first token's distance to my row
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
@@ -489,6 +558,10 @@ __device__ __forceinline__ void prefill_tile(const P& p) {
       const int tok0 = (2 * pp + i) * BS + 4 * kg;
       if constexpr (REL) {
         mx = fmaxf(mx, rel.scores(s[i], acc, p.scale_log2e, dist + (float)(i * BS), tok0, pos, on_edge));
+        continue;
+      }
+      if constexpr (TREE) {
+        mx = fmaxf(mx, tree.scores(s[i], acc, p.scale_log2e, tok0, on_edge));
         continue;
       }
       if (PREFIX && !col.select) {   // (wave-uniform: every column of the tile sees the whole prefix)
@@ -578,7 +651,7 @@ __device__ __forceinline__ void prefill_tile(const P& p) {
     return;
   }
   if (live) {
-    const float inv = 1.f / lsum;   // (a stored row attends at least to token 0 and its maximum contributes exp2(0): lsum >= 1)
+    const float inv = 1.f / lsum;   // (a stored row attends at least one token — TREE: itself — and its maximum contributes exp2(0): lsum >= 1)
     h16* op = p.out + ((int64_t)out_row * p.num_heads + head) * D + 4 * kg;
 #pragma unroll
     for (int t = 0; t < VT; ++t) {
@@ -599,6 +672,10 @@ __global__ void __launch_bounds__(WAVES * 64) pa_prefill_prefix_kernel(const Par
 template <int D, bool SPLIT = false, bool COOP = false, bool PACK = false>
 __global__ void __launch_bounds__(WAVES * 64) pa_prefill_rel_kernel(const RelParams p) {
   prefill_tile<D, SPLIT, COOP, PACK, false, true>(p);
+}
+template <int D, bool SPLIT = false, bool COOP = false, bool PACK = false>
+__global__ void __launch_bounds__(WAVES * 64) pa_prefill_tree_kernel(const TreeParams p) {
+  prefill_tile<D, SPLIT, COOP, PACK, false, false, true>(p);
 }
 
 }  // namespace prefill

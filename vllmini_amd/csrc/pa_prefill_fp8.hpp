@@ -52,6 +52,10 @@ struct RelParamsFp8 : ParamsFp8 {   // the REL kernels' argument, as RelParams
   const float* alibi_slopes;    // [num_heads] fp32, or NULL; the term is NOT scaled by kv_scale
   int32_t window;               // W of the sliding window, 0: none
 };
+struct TreeParamsFp8 : ParamsFp8 {  // the TREE kernels' argument, as TreeParams
+  const uint64_t* tree_mask;    // [num_tokens]
+};
+template <> inline constexpr int max_chunk_rows<TreeParamsFp8> = TREE_ROWS;
 
 // four E4M3 bytes -> four halves (two dwords of half pairs), element order kept
 __device__ __forceinline__ u32x2 e4m3x4_to_h16x4(uint32_t w) {
@@ -76,12 +80,15 @@ __device__ __forceinline__ h16x8 e4m3x8_to_h16x8(uint32_t w0, uint32_t w1) {
 // rows, not once per (sequence, head).  REL: its ALiBi / sliding-window form (pa_prefill_rel_fp8_kernel, argument RelParamsFp8:
 // walk bounds, edge-pair selects, relative partitions and the barrier rule are written there and shared through struct Rel); the
 // V bytes below the tile's window are cleared on the RAW dwords, before decoding, and the ALiBi term joins the score after
-// kv_scale: scale * kv_scale multiplies q . k alone.
-template <int D, bool SPLIT, bool COOP, bool PACK, bool PREFIX, bool REL = false, class P = ParamsFp8>
+// kv_scale: scale * kv_scale multiplies q . k alone.  TREE: its token-tree form (pa_prefill_tree_fp8_kernel, argument
+// TreeParamsFp8: the per-column word, the unselected context pairs, the guarded select on the chunk's pairs and the empty-share
+// rule are written there and shared through struct Tree); nothing about the bytes changes.
+template <int D, bool SPLIT, bool COOP, bool PACK, bool PREFIX, bool REL = false, bool TREE = false, class P = ParamsFp8>
 __device__ __forceinline__ void prefill_tile_fp8(const P& p) {
   static_assert(COOP || !PACK, "the head-packed form is cooperative by construction");
   static_assert(!PREFIX || (SPLIT && COOP && !PACK), "the shared-prefix form is a cooperative tile of partition 0, one query head");
   static_assert(!REL || !PREFIX, "ALiBi / sliding window over a shared prefix is not built");
+  static_assert(!TREE || (!PREFIX && !REL), "a token tree with a shared prefix, ALiBi or a sliding window is not built");
   constexpr int KG = D / 64;    // 64-dim groups of a K block: one 16-byte load, two MFMAs each
   constexpr int VT = D / 16;    // 16-dim tiles of the output: one dword per block, one MFMA each
   const int lane = threadIdx.x & 63;
@@ -108,6 +115,8 @@ __device__ __forceinline__ void prefill_tile_fp8(const P& p) {
     pp1 = min(npair, pp0 + (p.part_tokens >> 5));
   }
   const int blk_lo = REL ? rel.lo / BS : 0;                // REL: the first block the tile may read
+  Tree tree;
+  if constexpr (TREE) tree.init(p, col);
 
   // Q^T in the permuted k order of the K operand: for MFMA (g, j) dims 64g + 16kg + 8j .. +7
   const h16* qp = p.q + (int64_t)col.q_row * p.q_stride + (int64_t)head * D + 16 * kg;
@@ -170,7 +179,7 @@ __device__ __forceinline__ void prefill_tile_fp8(const P& p) {
     // ---- S^T = K . Q^T, scaled in fp32 (kv_scale included), causal mask selected ----
     float s[2][4];
     float mx = -INFINITY;
-    const bool on_edge = REL && rel.edge(pp);                                        // (wave-uniform)
+    const bool on_edge = REL ? rel.edge(pp) : TREE && tree.edge(pp);                 // (wave-uniform)
     const float dist = REL ? (float)(2 * pp * BS + 4 * kg - pos) : 0.f;             // REL: my first token's distance to my row
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
@@ -183,6 +192,10 @@ __device__ __forceinline__ void prefill_tile_fp8(const P& p) {
       const int tok0 = (2 * pp + i) * BS + 4 * kg;
       if constexpr (REL) {
         mx = fmaxf(mx, rel.scores(s[i], acc, p.scale_log2e, dist + (float)(i * BS), tok0, pos, on_edge));
+        continue;
+      }
+      if constexpr (TREE) {
+        mx = fmaxf(mx, tree.scores(s[i], acc, p.scale_log2e, tok0, on_edge));
         continue;
       }
       if (PREFIX && !col.select) {   // (wave-uniform: every column of the tile sees the whole prefix)
@@ -291,6 +304,10 @@ __global__ void __launch_bounds__(WAVES * 64) pa_prefill_prefix_fp8_kernel(const
 template <int D, bool SPLIT = false, bool COOP = false, bool PACK = false>
 __global__ void __launch_bounds__(WAVES * 64) pa_prefill_rel_fp8_kernel(const RelParamsFp8 p) {
   prefill_tile_fp8<D, SPLIT, COOP, PACK, false, true>(p);
+}
+template <int D, bool SPLIT = false, bool COOP = false, bool PACK = false>
+__global__ void __launch_bounds__(WAVES * 64) pa_prefill_tree_fp8_kernel(const TreeParamsFp8 p) {
+  prefill_tile_fp8<D, SPLIT, COOP, PACK, false, false, true>(p);
 }
 
 }  // namespace prefill

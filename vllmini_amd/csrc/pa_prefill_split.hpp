@@ -33,10 +33,15 @@ struct MergeParams {
   int32_t part_tokens, num_parts;
   float out_scale;              // 1, or kv_scale for fp8 pages
 };
+// The merge behind the TREE partition kernels (pa_prefill.hpp, TREE): the same fields and the same code — the type only gives the
+// guard the TREE kernels' bound on a chunk (a sequence with more than 64 rows wrote no partial, and gets no row of `out`).  A
+// partition of a row that holds none of its tokens carries (m = -3e38, l = 0, o = 0): weight exp2(-3e38 - M) = 0 below.
+struct MergeTreeParams : MergeParams {};
+template <> inline constexpr int max_chunk_rows<MergeTreeParams> = TREE_ROWS;
 
 // Grid: x = chunk * (num_seqs * num_heads) + seq * num_heads + head; chunk = 1024 / D consecutive rows of the sequence.
-template <int D>
-__global__ void __launch_bounds__(256) pa_prefill_merge_kernel(const MergeParams p) {
+template <int D, class P = MergeParams>
+__global__ void __launch_bounds__(256) pa_prefill_merge_kernel(const P p) {
   constexpr int LPR = D / 4;          // lanes per (row, head)
   constexpr int RPB = 256 / LPR;      // rows per workgroup
   const int items = p.num_seqs * p.num_heads;

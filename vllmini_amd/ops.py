@@ -622,6 +622,7 @@ def paged_attention_prefill(
     shared_prefix_len: Optional[int] = None,
     alibi_slopes: Optional[torch.Tensor] = None,
     sliding_window: Optional[int] = None,
+    tree_mask: Optional[torch.Tensor] = None,
 ) -> None:
     """Tiled causal attention of a chunk of query rows per sequence over the paged cache (extension: the reference runs its
     prefill as eager masked attention, gpt2.py:46-58); writes `out` in place, returns None.
@@ -680,12 +681,27 @@ def paged_attention_prefill(
     the same entries and kernels.  Either one together with `shared_prefix_len` raises: that combination is not built.
     Measured (profiles/prefill_rel.md, MI355X): the ALiBi term costs +5 % on a float16 prefill of 64 prompts and nothing
     measurable on decode rows; a window turns 38 into 12 - 17 us at 1 x 16 x 32 768 x 12 x 64 (W = 256 - 4 096) and 713 into 197 us for
-    256 decode rows over 4 096 tokens at W = 1 024; no measured cell lost."""
+    256 decode rows over 4 096 tokens at W = 1 024; no measured cell lost.
+
+    `tree_mask` (a contiguous int64 [num_tokens] tensor on the query's device: one 64-bit word per packed query row, read as
+    unsigned) makes every chunk a TOKEN TREE — the verification rows of a speculative decoder whose candidates branch — in every
+    form above but the shared prefix and over both page formats (the TREE kernels, csrc/pa_prefill.hpp).  With ctx = seq_lens[s] -
+    q_len, row j of sequence s's chunk attends every cached token t < ctx and chunk token ctx + i, i <= j, iff bit i of its word is
+    set.  Bit j (the row itself) always counts as set and bits above j are ignored: nodes come in a topological order, ancestors
+    first, and a word of -1 is plain causal attention for its row.  Row j's K / V sit at cached position ctx + j: write all q_len
+    rows (reshape_and_cache / reshape_and_cache_chunks) first.  Needs max_q_len <= 64; a sequence whose q_len on the device exceeds
+    64 writes nothing.  Form selection, the plans and the workspace are untouched: `cooperative`, `pack_heads`, `max_seq_len` and
+    `partition_tokens` mean what they mean above, and the tree kernels of the chosen form are launched.  None (default): every
+    launch above, bit for bit, through the same entries and kernels.  Together with `alibi_slopes`, `sliding_window` or
+    `shared_prefix_len` it raises: those combinations are not built.  Measurements: profiles/prefill_tree.md."""
     if sliding_window is not None and (isinstance(sliding_window, bool) or not isinstance(sliding_window, int) or sliding_window <= 0):
         raise RuntimeError(f"paged_attention_prefill: sliding_window must be a positive int, got {sliding_window!r}")
     rel = alibi_slopes is not None or sliding_window is not None
     if rel and shared_prefix_len is not None:
         raise RuntimeError("paged_attention_prefill: alibi_slopes / sliding_window together with shared_prefix_len is not built")
+    if tree_mask is not None and (rel or shared_prefix_len is not None):
+        raise RuntimeError("paged_attention_prefill: tree_mask together with alibi_slopes, sliding_window or shared_prefix_len "
+                           "is not built")
     if cooperative is not None and not isinstance(cooperative, bool):
         raise RuntimeError(f"paged_attention_prefill: cooperative must be True, False or None, got {cooperative!r}")
     if pack_heads is not None and not isinstance(pack_heads, bool):
@@ -717,12 +733,20 @@ def paged_attention_prefill(
     if alibi_slopes is not None and (alibi_slopes.dtype != torch.float32 or alibi_slopes.numel() != qs[1] or
                                      not alibi_slopes.is_contiguous()):
         raise RuntimeError("alibi_slopes must be a contiguous float32 [num_heads] tensor")      # (_pa_common's check)
+    if tree_mask is not None:
+        if tree_mask.dtype != torch.int64 or tree_mask.dim() != 1 or tree_mask.shape[0] != qs[0] or not tree_mask.is_contiguous():
+            raise RuntimeError("tree_mask must be a contiguous int64 [num_tokens] tensor (one 64-bit word per query row)")
+        if int(max_q_len) > 64:
+            raise RuntimeError(f"paged_attention_prefill: tree_mask holds one 64-bit word per row: max_q_len must be at most 64, "
+                               f"got {max_q_len}")
     index = query.get_device()
     dev = query.device
     if index < 0:
         _check_device("query", query, dev)
     if alibi_slopes is not None:
         _check_device("alibi_slopes", alibi_slopes, dev)
+    if tree_mask is not None:
+        _check_device("tree_mask", tree_mask, dev)
     _on("out", out, index, dev)
     _on("key_cache", key_cache, index, dev)
     _on("value_cache", value_cache, index, dev)
@@ -806,6 +830,26 @@ def paged_attention_prefill(
         slopes = (_ptr(alibi_slopes), window, form)
         rc = lib.vmi_paged_attention_prefill_rel_fp8(*args, *tail, float(kv_scale), *slopes) if fp8 else \
             lib.vmi_paged_attention_prefill_rel_f16(*args, *tail, *slopes)
+        if rc != 0:
+            _raise_native(rc)
+        return None
+    if tree_mask is not None:                           # the TREE kernels of the same form, on the same plan and workspace
+        if max_seq_len is None:                         # one launch, bounded by what the block table can hold
+            bound = min(16 * ts[1], 2 ** 31 - 32)
+            tail = (bound, max(32, (bound + 31) // 32 * 32), None, 0)
+        else:
+            plan = prefill_gqa_plan(num_tokens, num_heads, head_size, num_seqs, max_q_len, max_seq_len, num_kv_heads,
+                                    _num_cus(index), int(partition_tokens or 0)) if pack else \
+                prefill_split_plan(num_tokens, num_heads, head_size, num_seqs, max_q_len, max_seq_len, _num_cus(index),
+                                   int(partition_tokens or 0))
+            ws = prefill_workspace_for(index, plan[2], args[-1]) if plan[1] > 1 else None
+            if ws is None:                              # one partition (or capturing without a workspace): the single launch
+                tail = (int(max_seq_len), max(32, (int(max_seq_len) + 31) // 32 * 32), None, 0)
+            else:
+                tail = (int(max_seq_len), plan[0], ws.data_ptr(), ws.numel())
+        words = (tree_mask.data_ptr(), 2 if pack else 1 if coop else 0)
+        rc = lib.vmi_paged_attention_prefill_tree_fp8(*args, *tail, float(kv_scale), *words) if fp8 else \
+            lib.vmi_paged_attention_prefill_tree_f16(*args, *tail, *words)
         if rc != 0:
             _raise_native(rc)
         return None
